@@ -9,8 +9,15 @@ cardinality: K9/K10/K16), the fused hash+scatter partitioner (K4),
 RCCL all-to-allv over xGMI at N>1, and the consumer-side final
 aggregate (pre-combined passthrough at N=1).
 
+A plain run sets up, warms up, times --steps steps and prints one JSON
+result line.  --dump-outputs DIR additionally writes the last timed
+step's result (keys.npy, sums.npy; rows ordered by key, float64).
+--full is reserved for secondary measurements and checks; this benchmark
+has none (they live in benchmarks/), so it changes nothing today.
+
 Usage:
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs out/
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 bench.py --gpus 8 --steps 5 --warmup 2
 """
@@ -20,6 +27,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 import bigslice_amd as bs
@@ -27,6 +35,9 @@ import bigslice_amd as bs
 DEFAULT_ROWS_PER_GPU = 125_000_000
 DEFAULT_NKEYS = 1_000_000
 DEFAULT_SHARDS = 8
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0xD0E5
 
 _DATA = {}
 
@@ -53,6 +64,38 @@ def build_groupby(nshard):
 groupby_func = bs.func(build_groupby)
 
 
+def collect_output(res):
+    """Host copy of a result's (keys, sums) columns.  Collective at N>1
+    (rank 0 receives all rows, other ranks none)."""
+    keys, sums = [], []
+    for f in res.open():
+        keys.append(f.columns[0].cpu())
+        sums.append(f.columns[1].cpu())
+    if not keys:
+        z = torch.empty(0, dtype=torch.int64)
+        return z, z
+    return torch.cat(keys), torch.cat(sums)
+
+
+def dump_outputs(path, keys, sums):
+    """Write the group-by result as path/keys.npy and path/sums.npy
+    (float64; exact, both columns are far below 2**53).  Shard and
+    hash-table order is not part of the result, so rows are ordered by
+    key.  An output above DUMP_MAX_BYTES is cut to a fixed seeded sample
+    of those rows."""
+    order = torch.argsort(keys)
+    k = keys[order].numpy().astype(np.float64)
+    v = sums[order].numpy().astype(np.float64)
+    max_rows = DUMP_MAX_BYTES // (2 * 8)
+    if k.shape[0] > max_rows:
+        rs = np.random.RandomState(DUMP_SAMPLE_SEED)
+        pick = np.sort(rs.choice(k.shape[0], max_rows, replace=False))
+        k, v = k[pick], v[pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "keys.npy"), k)
+    np.save(os.path.join(path, "sums.npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -64,7 +107,16 @@ def main():
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--trace", type=str, default=None,
                     help="write a Chrome trace of the run to this path")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed step's result to "
+                         "DIR/keys.npy and DIR/sums.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run secondary measurements and checks "
+                         "(none here: they are separate scripts under "
+                         "benchmarks/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -97,8 +149,10 @@ def main():
             _DATA[shard] = gen_shard_data(shard, rows_per_shard,
                                           args.nkeys, device)
 
-    def step():
+    def step(keep=False):
         res = sess.run(groupby_func, nshard)
+        if keep:
+            return res
         res.discard()
 
     def sync():
@@ -111,10 +165,18 @@ def main():
         step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    # With --dump-outputs the last step's result outlives the timing.
+    last = step(keep=args.dump_outputs is not None)
     sync()
     elapsed = time.perf_counter() - t0
+
+    if last is not None:
+        out_keys, out_sums = collect_output(last)
+        last.discard()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out_keys, out_sums)
 
     # Max over ranks (whole-job time).
     if comm is not None:

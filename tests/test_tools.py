@@ -234,6 +234,40 @@ def test_bench_contract_cpu():
     assert d["value"] > 0
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+    # --dump-outputs writes the last timed step's group-by result; the
+    # inputs are seeded, so it is checked against a bincount of them.
+    import json
+    import subprocess
+    import sys as _sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rows, nkeys, shards = 80000, 1000, 8
+    out = subprocess.run(
+        [_sys.executable, "bench.py", "--rows-per-gpu", str(rows),
+         "--nkeys", str(nkeys), "--shards", str(shards), "--steps", "2",
+         "--warmup", "1", "--device", "cpu", "--full",
+         "--dump-outputs", str(tmp_path / "dump")],
+        capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(
+        [l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    keys = np.load(tmp_path / "dump" / "keys.npy")
+    sums = np.load(tmp_path / "dump" / "sums.npy")
+    assert keys.dtype == np.float64 and sums.dtype == np.float64
+    sys.path.insert(0, root)
+    import bench
+    allkeys = torch.cat([
+        bench.gen_shard_data(s, rows // shards, nkeys, "cpu")[0]
+        for s in range(shards)])
+    ref = torch.bincount(allkeys, minlength=nkeys).numpy()
+    present = np.nonzero(ref)[0]
+    assert np.array_equal(keys, present.astype(np.float64))
+    assert np.array_equal(sums, ref[present].astype(np.float64))
+
+
 def test_urls_example():
     sys.path.insert(0, "examples")
     import importlib
