@@ -32,3 +32,5 @@ from .runtime import (Result, Session, func, registry_digest, start)  # noqa
 from . import sliceio  # noqa
 from . import config  # noqa
 from . import strings  # noqa  (K17 device string hashing / dict ids)
+from . import exprs  # noqa  (K13 fused Map/Filter expressions)
+from .exprs import Expr, col, maximum, minimum, where  # noqa

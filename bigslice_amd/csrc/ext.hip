@@ -21,6 +21,7 @@
 #include "runs.hip"
 #include "vecagg.hip"
 #include "strings.hip"
+#include "expr.hip"
 
 namespace {
 
@@ -992,6 +993,150 @@ torch::Tensor radix_argsort(torch::Tensor keys) {
   return perm_out;
 }
 
+// K13: one launch of the expression interpreter (expr.hip) over a
+// batch.  code is the [n_instr, 2] int64 host image of the program
+// (packed fields, immediate); it is validated here, field by field,
+// before it reaches the device: every register, input slot and dtype
+// the kernel will index with is in range.  Returns the output columns
+// (n rows each) and, with a predicate, the survivor count as a
+// 1-element device tensor; the caller narrows after one readback.
+std::vector<torch::Tensor> expr_apply(
+    torch::Tensor code, int64_t n_pred, int64_t pred_reg,
+    std::vector<torch::Tensor> in_cols, std::vector<int64_t> out_regs,
+    std::vector<int64_t> out_dts) {
+  static const torch::ScalarType kDt[XD_N] = {
+      torch::kBool, torch::kInt32, torch::kInt64, torch::kFloat32,
+      torch::kFloat64};
+  TORCH_CHECK(!code.is_cuda() && code.scalar_type() == torch::kInt64 &&
+                  code.is_contiguous() && code.dim() == 2 &&
+                  code.size(1) == 2,
+              "expr_apply: code must be a [n, 2] int64 host tensor");
+  const int64_t n_total = code.size(0);
+  const int n_in = (int)in_cols.size(), n_out = (int)out_regs.size();
+  const bool has_pred = pred_reg >= 0;
+  TORCH_CHECK(n_total <= EXPR_MAX_INSTRS && n_pred >= 0 &&
+                  n_pred <= n_total && n_in >= 1 &&
+                  n_in <= EXPR_MAX_IN && n_out >= 1 &&
+                  n_out <= EXPR_MAX_OUT && out_dts.size() == out_regs.size() &&
+                  pred_reg < EXPR_MAX_REGS && (has_pred || n_pred == 0),
+              "expr_apply: program over the kernel's limits");
+  ExprProgram P;
+  memset(&P, 0, sizeof(P));
+  int nregs = (int)pred_reg + 1;  // registers the program names
+  const int64_t n = in_cols[0].size(0);
+  for (int k = 0; k < n_in; ++k) {
+    const auto& c = in_cols[k];
+    TORCH_CHECK(c.is_cuda() && c.is_contiguous() && c.dim() == 1 &&
+                    c.size(0) == n &&
+                    c.device() == in_cols[0].device(),
+                "expr_apply: inputs must be contiguous 1-D device "
+                "columns of one length");
+    int dt = -1;
+    for (int d = 0; d < XD_N; ++d)
+      if (c.scalar_type() == kDt[d]) dt = d;
+    TORCH_CHECK(dt >= 0, "expr_apply: unsupported input dtype ",
+                c.scalar_type());
+    P.in_ptr[k] = c.data_ptr();
+    P.in_dt[k] = (uint8_t)dt;
+  }
+  const int64_t* w = code.data_ptr<int64_t>();
+  P.pred_begin = 0;
+  P.out_begin = (int32_t)n_pred;
+  for (int64_t i = 0; i < n_total; ++i) {
+    const uint64_t x = (uint64_t)w[2 * i];
+    const int op = x & 0xff, dt = (x >> 8) & 0xff, dst = (x >> 16) & 0xff,
+              a = (x >> 24) & 0xff, b = (x >> 32) & 0xff,
+              c = (x >> 40) & 0xff;
+    TORCH_CHECK(op < XO_N && dt < XD_N && dst < EXPR_MAX_REGS &&
+                    b < EXPR_MAX_REGS && c < EXPR_MAX_REGS &&
+                    (x >> 49) == 0,
+                "expr_apply: malformed instruction ", i);
+    if (op == XO_LOAD) {
+      // a section's LOADs lead it; the kernel runs them from ld_reg
+      const int sec = i < n_pred ? 0 : 1;
+      int32_t& begin = sec ? P.out_begin : P.pred_begin;
+      TORCH_CHECK(a < n_in && P.in_dt[a] == dt && begin == i,
+                  "expr_apply: LOAD of a missing or mistyped input, or "
+                  "not at the head of its section");
+      begin = (int32_t)i + 1;
+      (sec ? P.mask_out : P.mask_pred) |= 1u << a;
+      P.ld_reg[sec][a] = (uint8_t)dst;
+    } else {
+      TORCH_CHECK(a < EXPR_MAX_REGS && (op != XO_CAST || c < XD_N),
+                  "expr_apply: malformed instruction ", i);
+    }
+    nregs = std::max(nregs, dst + 1);
+    P.ins[i].w = x;
+    P.ins[i].imm = (uint64_t)w[2 * i + 1];
+  }
+  P.n_pred = (int32_t)n_pred;
+  P.n_total = (int32_t)n_total;
+  P.n_in = n_in;
+  P.n_out = n_out;
+  P.pred_reg = (int32_t)pred_reg;
+  std::vector<torch::Tensor> outs;
+  for (int o = 0; o < n_out; ++o) {
+    TORCH_CHECK(out_regs[o] >= 0 && out_regs[o] < EXPR_MAX_REGS &&
+                    out_dts[o] >= 0 && out_dts[o] < XD_N,
+                "expr_apply: malformed output ", o);
+    outs.push_back(torch::empty(
+        {n}, in_cols[0].options().dtype(kDt[out_dts[o]])));
+    P.out_ptr[o] = outs.back().data_ptr();
+    P.out_dt[o] = (uint8_t)out_dts[o];
+    P.out_reg[o] = (uint8_t)out_regs[o];
+    nregs = std::max(nregs, (int)out_regs[o] + 1);
+  }
+  auto count = torch::zeros({1}, in_cols[0].options().dtype(torch::kInt64));
+  if (has_pred) outs.push_back(count);
+  if (n == 0) return outs;
+  constexpr int64_t tile = (int64_t)EXPR_BLOCK * EXPR_IPT;
+  const int64_t ntiles = (n + tile - 1) / tile;
+  TORCH_CHECK(ntiles < (1ll << 31), "expr_apply: batch too large");
+  auto stream = current_stream();
+  // J slabs per decode, the most the 16-slot register file allows; a
+  // register never written is never read for a result that matters,
+  // but it is still indexed: count every register field
+  for (int64_t i = 0; i < n_total; ++i) {
+    const uint64_t x = P.ins[i].w;
+    const int op = x & 0xff;
+    if (op == XO_LOAD || op == XO_CONST) continue;
+    nregs = std::max(nregs, (int)((x >> 24) & 0xff) + 1);
+    nregs = std::max(nregs, (int)((x >> 32) & 0xff) + 1);
+    if (op == XO_WHERE)
+      nregs = std::max(nregs, (int)((x >> 40) & 0xff) + 1);
+  }
+  TORCH_CHECK(nregs >= 1 && nregs <= EXPR_MAX_REGS);
+  const int J = nregs <= 4 ? 4 : (nregs <= 8 ? 2 : 1);
+  const size_t lds = (size_t)nregs * J * sizeof(ExprRegs);
+  int64_t* count_ptr = nullptr;
+  unsigned long long* state_ptr = nullptr;
+  torch::Tensor state;
+  if (has_pred) {
+    // per-tile lookback words, zeroed on the launch stream every time
+    state = torch::empty({ntiles},
+                         in_cols[0].options().dtype(torch::kInt64));
+    HIP_CHECK(hipMemsetAsync(state.data_ptr(), 0, (size_t)ntiles * 8,
+                             stream));
+    count_ptr = count.data_ptr<int64_t>();
+    state_ptr = (unsigned long long*)state.data_ptr<int64_t>();
+  }
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((int)ntiles), dim3(EXPR_BLOCK), lds,
+                       stream, P, n, count_ptr, state_ptr);
+  };
+  if (has_pred) {
+    if (J == 4) launch(k_expr<true, 4>);
+    else if (J == 2) launch(k_expr<true, 2>);
+    else launch(k_expr<true, 1>);
+  } else {
+    if (J == 4) launch(k_expr<false, 4>);
+    else if (J == 2) launch(k_expr<false, 2>);
+    else launch(k_expr<false, 1>);
+  }
+  HIP_CHECK(hipGetLastError());
+  return outs;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1039,4 +1184,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("radix_sort_kv", &radix_sort_kv,
         "direct (key, 8-byte value) radix sort");
   m.def("slot_pids", &slot_pids, "table-slot-range partition ids");
+  m.def("expr_apply", &expr_apply,
+        "fused Map/Filter expression interpreter (K13)");
 }

@@ -557,3 +557,69 @@ def radix_sort_keys(keys: torch.Tensor) -> torch.Tensor:
             _require("radix_sort_keys")
         return torch.sort(keys).values
     return _C.radix_sort_keys(keys)
+
+
+# -- fused Map/Filter expressions (K13) -------------------------------------
+
+# rows per tile of the expression kernel (csrc/expr.hip: 256 x 32)
+EXPR_TILE_ROWS = 8192
+
+_EXPR_DTYPES = (torch.bool, torch.int32, torch.int64, torch.float32,
+                torch.float64)
+
+
+def expr_supported(program, frame) -> bool:
+    """True when expr_apply can run this (native-eligible) program on
+    this frame: every column it reads or writes is a dense contiguous
+    device tensor of a vocabulary dtype.  Pass-through columns of a
+    predicate-free program are not touched and may be anything."""
+    cols = [frame.columns[i] for i in program.inputs]
+    on_gpu = any(isinstance(c, torch.Tensor) and c.is_cuda
+                 for c in frame.columns)
+    if _C is None:
+        if on_gpu and not ALLOW_FALLBACK:
+            _require("expr_apply")
+        return False
+    # (a column whose dtype is not the schema's the program was typed
+    # from also takes the eval path, where torch promotes what it sees)
+    return program.eligible and all(
+        isinstance(c, torch.Tensor) and c.is_cuda and c.dim() == 1
+        and c.is_contiguous() and c.dtype in _EXPR_DTYPES and c.dtype == dt
+        for c, dt in zip(cols, program.in_dtypes))
+
+
+def expr_apply(program, cols):
+    """Run a compiled expression program (exprs.compile_program) over
+    the frame columns ``cols`` in one kernel launch.  Returns
+    (out_cols, count): count is None without a predicate; with one, the
+    outputs hold the ``count`` surviving rows in input order."""
+    from ..exprs import _DT_CODE
+    _require("expr_apply")
+    ins = [cols[i] for i in program.inputs]
+    regs = [v for kind, v in program.outputs if kind == "reg"]
+    dts = [_DT_CODE[dt] for (kind, _), dt in
+           zip(program.outputs, program.out_dtypes) if kind == "reg"]
+    has_pred = program.pred_reg >= 0
+    n = ins[0].shape[0] if ins else 0
+    if n == 0 or not regs:
+        # nothing to launch: an empty batch, or only pass-through columns
+        outs = [torch.empty(0, dtype=dt, device=ins[0].device)
+                for (kind, _), dt in zip(program.outputs,
+                                         program.out_dtypes)
+                if kind == "reg"]
+        res = iter(outs)
+        return ([next(res) if kind == "reg" else cols[v]
+                 for kind, v in program.outputs],
+                0 if has_pred else None)
+    got = _C.expr_apply(program.code(), program.n_pred, program.pred_reg,
+                        ins, regs, dts)
+    count = None
+    if has_pred:
+        count = int(got.pop().item())  # the one readback per batch
+        # a selective filter must not pin the n-row allocation: at most
+        # 2x its own bytes stay referenced
+        got = [o[:count].clone() if 2 * count <= n else o[:count]
+               for o in got]
+    res = iter(got)
+    return ([next(res) if kind == "reg" else cols[v]
+             for kind, v in program.outputs], count)

@@ -101,13 +101,57 @@ class _PipelinedSlice(Slice):
                          combiner=combiner)
 
 
+def _expr_reader(src: Reader, in_schema: Schema, exprs, pred,
+                 prefix) -> Reader:
+    """Reader of an expression Map (exprs) or Filter (pred).  An
+    unstarted ExprReader below folds in: the chain becomes one reader,
+    hence one kernel launch per batch, over the original source.  Any
+    other reader (a materialize/shuffle/cache boundary, a lambda stage)
+    is simply the source."""
+    from ..exprs import ExprReader, ExprSpec
+    if isinstance(src, ExprReader) and not src.started:
+        spec, src = src.spec, src.src
+    else:
+        spec = ExprSpec(in_schema, None, None, None)
+    spec = spec.then_map(exprs, prefix) if exprs is not None \
+        else spec.then_filter(pred)
+    return ExprReader(src, spec)
+
+
 class Map(_PipelinedSlice):
-    def __init__(self, dep: Slice, fn: Callable, out_schema=None,
+    """fn is a vectorized callable over whole columns (or a row function
+    with rowwise=True), or an Expr / sequence of Exprs (exprs.py), one
+    per output column."""
+
+    def __init__(self, dep: Slice, fn, out_schema=None,
                  rowwise: bool = False, prefix: int = None):
         self.fn = fn
         self.rowwise = rowwise
+        self.exprs = None
         in_schema = dep.schema
-        if out_schema is not None:
+        from ..exprs import Expr, is_exprs
+        if is_exprs(fn):
+            if rowwise:
+                raise TypeError("rowwise=True does not apply to an Expr "
+                                "Map")
+            exprs = [fn] if isinstance(fn, Expr) else list(fn)
+            exprs = [e.bind(in_schema) for e in exprs]
+            if out_schema is not None:
+                want = out_schema if isinstance(out_schema, Schema) \
+                    else schema_of(*out_schema, prefix=prefix)
+                if want.num_columns != len(exprs):
+                    raise TypeError(
+                        f"{len(exprs)} Exprs for an out_schema of "
+                        f"{want.num_columns} columns")
+                exprs = [e if e.dtype == dt else e.to(dt)
+                         for e, dt in zip(exprs, want.dtypes)]
+                schema = want
+            else:
+                schema = Schema(
+                    [e.dtype for e in exprs],
+                    min(prefix or in_schema.prefix, len(exprs)) or None)
+            self.exprs = exprs
+        elif out_schema is not None:
             schema = out_schema if isinstance(out_schema, Schema) \
                 else schema_of(*out_schema, prefix=prefix)
         elif rowwise:
@@ -124,6 +168,9 @@ class Map(_PipelinedSlice):
 
     def reader(self, shard, dep_readers, ctx: TaskContext) -> Reader:
         src = dep_readers[0]
+        if self.exprs is not None:
+            return _expr_reader(src, self.deps[0].slice.schema,
+                                self.exprs, None, self.schema.prefix)
         fn, rowwise, schema = self.fn, self.rowwise, self.schema
         if rowwise and ctx.device != "cpu":
             _warn_host_rowwise("Map")
@@ -143,13 +190,29 @@ class Map(_PipelinedSlice):
 
 
 class Filter(_PipelinedSlice):
-    def __init__(self, dep: Slice, fn: Callable, rowwise: bool = False):
+    """fn is a vectorized callable returning a keep mask (or a row
+    predicate with rowwise=True), or a bool-typed Expr (exprs.py)."""
+
+    def __init__(self, dep: Slice, fn, rowwise: bool = False):
         self.fn = fn
         self.rowwise = rowwise
+        self.pred = None
+        from ..exprs import Expr
+        if isinstance(fn, Expr):
+            if rowwise:
+                raise TypeError("rowwise=True does not apply to an Expr "
+                                "Filter")
+            pred = fn.bind(dep.schema)
+            if pred.dtype != torch.bool:
+                raise TypeError(
+                    f"Filter predicate has dtype {pred.dtype}, not bool")
+            self.pred = pred
         super().__init__(dep, dep.schema, "filter")
 
     def reader(self, shard, dep_readers, ctx: TaskContext) -> Reader:
         src = dep_readers[0]
+        if self.pred is not None:
+            return _expr_reader(src, self.schema, None, self.pred, None)
         fn, rowwise = self.fn, self.rowwise
         if rowwise and ctx.device != "cpu":
             _warn_host_rowwise("Filter")
