@@ -16,6 +16,7 @@
 
 #include "hash_partition.hip"
 #include "groupby.hip"
+#include "groupby_part.hip"
 #include "sort.hip"
 #include "radix.hip"
 #include "runs.hip"
@@ -288,6 +289,113 @@ void groupby_insert_lds(torch::Tensor keys, torch::Tensor vals,
                      flags.data_ptr<int32_t>() + 1, max_probes, rpb,
                      (int32_t)force,
                      hits.numel() ? (uint32_t*)hits.data_ptr() : nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Partitioned LDS pre-aggregation (single int64 SUM value): see
+// groupby_part.hip.  Histogram, offsets and scatter; returns the
+// partitioned (key, value) pairs [n, 2] and the rows per bucket.
+std::tuple<torch::Tensor, torch::Tensor> part_scatter_impl(
+    const torch::Tensor& keys, const torch::Tensor& vals, int64_t cap,
+    int64_t nbuckets) {
+  int64_t n = keys.size(0);
+  TORCH_CHECK(n > 0 && n < (int64_t(1) << 31), "1 <= rows < 2^31");
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && cap <= (int64_t(1) << 31),
+              "capacity must be 2^k");
+  TORCH_CHECK(nbuckets >= 2 && nbuckets <= GBP_MAX_BUCKETS &&
+                  (nbuckets & (nbuckets - 1)) == 0 && nbuckets <= cap,
+              "nbuckets must be a power of two in [2, ", GBP_MAX_BUCKETS,
+              "] and at most the capacity");
+  const uint32_t seed = 0x9acb0442u;
+  const uint32_t mask = (uint32_t)(cap - 1);
+  uint32_t shift = 0;
+  while ((cap >> shift) > nbuckets) ++shift;
+  const uint32_t nb = (uint32_t)nbuckets;
+  const int64_t ntiles = (n + GBP_SCATTER_ROWS - 1) / GBP_SCATTER_ROWS;
+  auto opts32 = keys.options().dtype(torch::kInt32);
+  auto hist = torch::empty({ntiles * nbuckets}, opts32);
+  auto totals = torch::empty({nbuckets}, opts32);
+  auto pairs = torch::empty({n, 2}, keys.options());
+  auto stream = current_stream();
+  hipLaunchKernelGGL(k_gbp_hist, dim3((uint32_t)ntiles), dim3(GBP_THREADS),
+                     0, stream, keys.data_ptr<int64_t>(), n, nb, seed, mask,
+                     shift, (uint32_t*)hist.data_ptr<int32_t>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gbp_offsets, dim3((nb + 63) / 64),
+                     dim3(GBP_OFF_THREADS), 0, stream,
+                     (uint32_t*)hist.data_ptr<int32_t>(), ntiles, nb,
+                     (uint32_t*)totals.data_ptr<int32_t>());
+  HIP_CHECK(hipGetLastError());
+  const int64_t per_xcd = (ntiles + 7) / 8;
+  hipLaunchKernelGGL(k_gbp_scatter, dim3((uint32_t)(8 * per_xcd)),
+                     dim3(GBP_THREADS), 0, stream,
+                     keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
+                     ntiles, nb, seed, mask, shift,
+                     (const uint32_t*)hist.data_ptr<int32_t>(),
+                     (const uint32_t*)totals.data_ptr<int32_t>(),
+                     (GbPair*)pairs.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  return {pairs, totals};
+}
+
+void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
+                         torch::Tensor tkeys, torch::Tensor tab,
+                         torch::Tensor flags, int64_t max_probes,
+                         int64_t nbuckets) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
+  TORCH_CHECK(vals.scalar_type() == torch::kInt64 &&
+              vals.size(0) == keys.size(0));
+  TORCH_CHECK(tab.scalar_type() == torch::kInt64);
+  keys = keys.contiguous();
+  vals = vals.contiguous();
+  int64_t n = keys.size(0);
+  if (n == 0) return;
+  int64_t cap = tkeys.size(0) - 1;
+  auto parts = part_scatter_impl(keys, vals, cap, nbuckets);
+  const torch::Tensor& pairs = std::get<0>(parts);
+  const uint32_t seed = 0x9acb0442u;
+  const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
+  hipLaunchKernelGGL(k_gbp_aggregate, dim3((uint32_t)ntiles),
+                     dim3(GBP_THREADS), 0, current_stream(),
+                     (const GbPair*)pairs.data_ptr<int64_t>(), n,
+                     tkeys.data_ptr<int64_t>(),
+                     (long long*)tab.data_ptr<int64_t>(), cap, seed,
+                     flags.data_ptr<int32_t>(),
+                     flags.data_ptr<int32_t>() + 1, max_probes);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The scatter alone (tests, kernel timing): (pairs [n, 2], rows per
+// bucket [nbuckets]).
+std::tuple<torch::Tensor, torch::Tensor> groupby_part_scatter(
+    torch::Tensor keys, torch::Tensor vals, int64_t cap,
+    int64_t nbuckets) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
+  TORCH_CHECK(vals.scalar_type() == torch::kInt64 &&
+              vals.size(0) == keys.size(0));
+  return part_scatter_impl(keys.contiguous(), vals.contiguous(), cap,
+                           nbuckets);
+}
+
+// Aggregate pass alone over already partitioned pairs (kernel timing).
+void groupby_part_aggregate(torch::Tensor pairs, torch::Tensor tkeys,
+                            torch::Tensor tab, torch::Tensor flags,
+                            int64_t max_probes) {
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt64 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(1) == 2);
+  int64_t n = pairs.size(0);
+  if (n == 0) return;
+  int64_t cap = tkeys.size(0) - 1;
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0);
+  const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
+  hipLaunchKernelGGL(k_gbp_aggregate, dim3((uint32_t)ntiles),
+                     dim3(GBP_THREADS), 0, current_stream(),
+                     (const GbPair*)pairs.data_ptr<int64_t>(), n,
+                     tkeys.data_ptr<int64_t>(),
+                     (long long*)tab.data_ptr<int64_t>(), cap, 0x9acb0442u,
+                     flags.data_ptr<int32_t>(),
+                     flags.data_ptr<int32_t>() + 1, max_probes);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1149,6 +1257,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "hash-aggregate insert pass (K9)");
   m.def("groupby_insert_lds", &groupby_insert_lds,
         "two-level LDS+global insert (int64 sum)");
+  m.def("groupby_insert_part", &groupby_insert_part,
+        "partitioned LDS pre-aggregating insert (single i64 sum)");
+  m.def("groupby_part_scatter", &groupby_part_scatter,
+        "bucket scatter of the partitioned insert");
+  m.def("groupby_part_aggregate", &groupby_part_aggregate,
+        "aggregate pass of the partitioned insert");
+  m.attr("GBP_TILE_ROWS") = (int64_t)GBP_TILE_ROWS;
+  m.attr("GBP_LDS_SLOTS") = (int64_t)GBP_LDS_SLOTS;
+  m.attr("GBP_MAX_BUCKETS") = (int64_t)GBP_MAX_BUCKETS;
   m.def("groupby_insert_mlp", &groupby_insert_mlp,
         "multi-row software-pipelined insert (int64 sum)");
   m.def("groupby_insert_packed_rep", &groupby_insert_packed_rep,

@@ -1,0 +1,283 @@
+// K19: partitioned LDS pre-aggregation for the single-int64-SUM group-by.
+//
+// The one-pass insert (groupby.hip) pays one memory-side atomic per row.
+// At mid cardinality (~1M keys, a few rows per key per batch) neither the
+// 1024-slot LDS tier nor replication removes any of them.  This path
+// makes duplicates of a key neighbours first, so a workgroup-private LDS
+// table can absorb them and only ONE global atomic per distinct key per
+// tile reaches the table:
+//
+//   1. k_gbp_hist     per-tile LDS histogram of bucket ids -> tiles x B
+//   2. k_gbp_offsets  column-wise exclusive scan of that matrix (in
+//                     place) + per-bucket totals
+//   3. k_gbp_scatter  re-reads the tile, reorders it by bucket in LDS and
+//                     writes (key, value) as 16-byte pairs, each bucket's
+//                     rows of the tile as one contiguous run
+//   4. k_gbp_aggregate fixed tiles of the partitioned buffer -> LDS hash
+//                     table (LDS CAS + 64-bit LDS add) -> one
+//                     gb_global_insert_sum per occupied LDS slot
+//
+// Bucket id = high bits of the global table slot hash, so the rows of a
+// bucket also share a table range.  The global table, its probing, the
+// sentinel slot and the overflow flag are exactly those of groupby.hip:
+// the LDS tables are private pre-aggregators only, and batches inserted
+// by this path and by k_groupby_insert mix freely in one table.
+//
+// No kernel waits on another workgroup; ordering is by launch.
+
+#include <hip/hip_runtime.h>
+
+#include "columns.h"
+
+#define GBP_THREADS 512
+// rows per histogram/scatter tile: 64 KiB of staged pairs, two
+// workgroups per CU
+#define GBP_SCATTER_ROWS 4096
+// pairs per aggregate tile and slots of its LDS table (64 KiB: two
+// workgroups per CU)
+#define GBP_TILE_ROWS 8192
+#define GBP_LDS_SLOTS 4096
+#define GBP_LDS_BITS 12
+#define GBP_LDS_PROBES 8
+#define GBP_MAX_BUCKETS 1024
+
+struct __attribute__((aligned(16))) GbPair {
+  long long k;
+  long long v;
+};
+
+// Sentinel-key rows go to bucket 0; the aggregate pass routes them to the
+// reserved slot.
+__device__ __forceinline__ uint32_t gbp_bucket(long long k, uint32_t seed,
+                                               uint32_t mask,
+                                               uint32_t shift) {
+  if (k == GB_SENTINEL) return 0;
+  return (mm3_u64((uint64_t)k, seed) & mask) >> shift;
+}
+
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_hist(
+    const int64_t* keys, int64_t n, uint32_t nb, uint32_t seed,
+    uint32_t mask, uint32_t shift, uint32_t* hist) {
+  __shared__ uint32_t lh[GBP_MAX_BUCKETS];
+  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) lh[b] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * GBP_SCATTER_ROWS;
+#pragma unroll
+  for (int j = 0; j < GBP_SCATTER_ROWS / GBP_THREADS; ++j) {
+    const int64_t i = base + j * GBP_THREADS + threadIdx.x;
+    if (i < n) atomicAdd(&lh[gbp_bucket(keys[i], seed, mask, shift)], 1u);
+  }
+  __syncthreads();
+  uint32_t* row = hist + (int64_t)blockIdx.x * nb;
+  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) row[b] = lh[b];
+}
+
+// In-place exclusive scan down each bucket column of the tiles x B
+// matrix, plus the column totals.  One workgroup per 64 adjacent columns
+// (a wave reads 64 consecutive counters of one tile: coalesced); its 16
+// waves split the tile axis, exchange chunk sums through LDS, then
+// rewrite their chunk.  Loads are issued in groups of 8 before the
+// dependent stores so a chunk costs ~tiles/128 round trips, not
+// tiles/16.
+#define GBP_OFF_THREADS 1024
+#define GBP_OFF_WAVES (GBP_OFF_THREADS / 64)
+
+extern "C" __global__ __launch_bounds__(GBP_OFF_THREADS) void k_gbp_offsets(
+    uint32_t* hist, int64_t ntiles, uint32_t nb, uint32_t* totals) {
+  __shared__ uint32_t wsum[GBP_OFF_WAVES][64];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const uint32_t col = blockIdx.x * 64 + lane;
+  const bool ok = col < nb;
+  const int64_t chunk = (ntiles + GBP_OFF_WAVES - 1) / GBP_OFF_WAVES;
+  const int64_t t0 = min((int64_t)w * chunk, ntiles);
+  const int64_t t1 = min(t0 + chunk, ntiles);
+  uint32_t s = 0;
+  if (ok) {
+#pragma unroll 8
+    for (int64_t t = t0; t < t1; ++t) s += hist[t * nb + col];
+  }
+  wsum[w][lane] = s;
+  __syncthreads();
+  uint32_t run = 0;
+  for (int w2 = 0; w2 < w; ++w2) run += wsum[w2][lane];
+  if (w == GBP_OFF_WAVES - 1 && ok) totals[col] = run + s;
+  if (!ok) return;
+  int64_t t = t0;
+  for (; t + 8 <= t1; t += 8) {
+    uint32_t v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = hist[(t + j) * nb + col];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      hist[(t + j) * nb + col] = run;
+      run += v[j];
+    }
+  }
+  for (; t < t1; ++t) {
+    const uint32_t v = hist[t * nb + col];
+    hist[t * nb + col] = run;
+    run += v;
+  }
+}
+
+// In-place exclusive scan of a[0..nb), nb <= 2 * GBP_THREADS, by the whole
+// workgroup (two adjacent entries per thread).  Ends with a barrier.
+__device__ __forceinline__ void gbp_block_scan(uint32_t* a, uint32_t nb,
+                                               uint32_t* wtmp) {
+  const uint32_t i0 = 2 * threadIdx.x;
+  const uint32_t x0 = i0 < nb ? a[i0] : 0;
+  const uint32_t x1 = i0 + 1 < nb ? a[i0 + 1] : 0;
+  const uint32_t s = x0 + x1;
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  uint32_t run = s;  // inclusive wave scan
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(run, off);
+    if (lane >= off) run += up;
+  }
+  if (lane == 63) wtmp[w] = run;
+  __syncthreads();
+  uint32_t base = 0;
+  for (int w2 = 0; w2 < w; ++w2) base += wtmp[w2];
+  const uint32_t excl = base + run - s;
+  if (i0 < nb) a[i0] = excl;
+  if (i0 + 1 < nb) a[i0 + 1] = excl + x0;
+  __syncthreads();
+}
+
+// hist holds the scanned matrix (offset of the tile's run inside each
+// bucket), totals the rows per bucket.  Consecutive tiles are mapped to
+// workgroups 8 apart so neighbouring runs of a bucket are written
+// through the same XCD's L2 and merge into whole lines there.
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_scatter(
+    const int64_t* keys, const int64_t* vals, int64_t n, int64_t ntiles,
+    uint32_t nb, uint32_t seed, uint32_t mask, uint32_t shift,
+    const uint32_t* hist, const uint32_t* totals, GbPair* out) {
+  __shared__ GbPair stage[GBP_SCATTER_ROWS];
+  __shared__ uint32_t lstart[GBP_MAX_BUCKETS];
+  __shared__ uint32_t delta[GBP_MAX_BUCKETS];
+  __shared__ uint32_t wtmp[GBP_THREADS / 64];
+  const int64_t per_xcd = (ntiles + 7) / 8;
+  const int64_t tile = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  if (tile >= ntiles) return;
+  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) {
+    lstart[b] = 0;
+    delta[b] = totals[b];
+  }
+  __syncthreads();
+  constexpr int R = GBP_SCATTER_ROWS / GBP_THREADS;
+  const int64_t base = tile * GBP_SCATTER_ROWS;
+  const uint32_t cnt = (uint32_t)min((int64_t)GBP_SCATTER_ROWS, n - base);
+  long long k[R], v[R];
+  uint32_t br[R];  // bucket << 16 | rank of the row inside its bucket
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const uint32_t p = j * GBP_THREADS + threadIdx.x;
+    if (p < cnt) {
+      k[j] = keys[base + p];
+      v[j] = vals[base + p];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const uint32_t p = j * GBP_THREADS + threadIdx.x;
+    if (p < cnt) {
+      const uint32_t b = gbp_bucket(k[j], seed, mask, shift);
+      br[j] = (b << 16) | atomicAdd(&lstart[b], 1u);
+    }
+  }
+  __syncthreads();
+  gbp_block_scan(lstart, nb, wtmp);  // start of each bucket in the tile
+  gbp_block_scan(delta, nb, wtmp);   // start of each bucket in `out`
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const uint32_t p = j * GBP_THREADS + threadIdx.x;
+    if (p < cnt) {
+      GbPair pr;
+      pr.k = k[j];
+      pr.v = v[j];
+      stage[lstart[br[j] >> 16] + (br[j] & 0xffffu)] = pr;
+    }
+  }
+  // destination of staged position p of bucket b = delta[b] + p
+  // (uint32 arithmetic wraps consistently; n < 2^31)
+  const uint32_t* hrow = hist + tile * nb;
+  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS)
+    delta[b] += hrow[b] - lstart[b];
+  __syncthreads();
+  for (uint32_t p = threadIdx.x; p < cnt; p += GBP_THREADS) {
+    const GbPair pr = stage[p];
+    const uint32_t b = gbp_bucket(pr.k, seed, mask, shift);
+    const uint32_t d = delta[b] + p;
+    if (d < n) out[d] = pr;  // always true; keeps a bad offset in bounds
+  }
+}
+
+// One row through the tile's LDS table; false when the bounded probe
+// chain is exhausted (caller goes to the global table).  The LDS index
+// remixes the whole slot hash: rows of a tile share its bucket bits.
+__device__ __forceinline__ bool gbp_lds_add(long long k, long long v,
+                                            long long* lk, long long* lv,
+                                            uint32_t seed) {
+  uint32_t h = (mm3_u64((uint64_t)k, seed) * 0x9e3779b1u) >>
+               (32 - GBP_LDS_BITS);
+  for (int p = 0; p < GBP_LDS_PROBES; ++p) {
+    long long cur = lk[h];
+    if (cur == GB_SENTINEL) {
+      const long long prev = atomicCAS((unsigned long long*)&lk[h],
+                                       (unsigned long long)GB_SENTINEL,
+                                       (unsigned long long)k);
+      cur = (prev == GB_SENTINEL) ? k : prev;
+    }
+    if (cur == k) {
+      atomicAdd((unsigned long long*)&lv[h], (unsigned long long)v);
+      return true;
+    }
+    h = (h + 1) & (GBP_LDS_SLOTS - 1);
+  }
+  return false;
+}
+
+// Grid = ceil(n / GBP_TILE_ROWS) over fixed tiles of the partitioned
+// buffer: a tile may span bucket boundaries and a skewed bucket spans
+// many tiles, so no workgroup's work depends on the key distribution.
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_aggregate(
+    const GbPair* pairs, int64_t n, int64_t* tkeys, long long* tab,
+    int64_t cap, uint32_t seed, int32_t* sentinel_seen, int32_t* overflow,
+    int64_t max_probes) {
+  __shared__ long long lk[GBP_LDS_SLOTS];
+  __shared__ long long lv[GBP_LDS_SLOTS];
+  for (int s = threadIdx.x; s < GBP_LDS_SLOTS; s += GBP_THREADS) {
+    lk[s] = GB_SENTINEL;
+    lv[s] = 0;
+  }
+  __syncthreads();
+  const uint64_t gmask = (uint64_t)cap - 1;
+  const int64_t base = (int64_t)blockIdx.x * GBP_TILE_ROWS;
+  // G loads in flight per thread before the first LDS probe
+  constexpr int G = 8;
+  for (int j0 = 0; j0 < GBP_TILE_ROWS / GBP_THREADS; j0 += G) {
+    GbPair pr[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int64_t i = base + (j0 + j) * GBP_THREADS + threadIdx.x;
+      if (i < n) pr[j] = pairs[i];
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int64_t i = base + (j0 + j) * GBP_THREADS + threadIdx.x;
+      if (i < n && (pr[j].k == GB_SENTINEL ||
+                    !gbp_lds_add(pr[j].k, pr[j].v, lk, lv, seed)))
+        gb_global_insert_sum(pr[j].k, pr[j].v, tkeys, tab, gmask, cap, seed,
+                             sentinel_seen, overflow, max_probes);
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < GBP_LDS_SLOTS; s += GBP_THREADS) {
+    const long long k = lk[s];
+    if (k != GB_SENTINEL)
+      gb_global_insert_sum(k, lv[s], tkeys, tab, gmask, cap, seed,
+                           sentinel_seen, overflow, max_probes);
+  }
+}

@@ -96,6 +96,26 @@ _GB_VAL_DTYPES = (torch.int64, torch.int32, torch.float32, torch.float64)
 GB_SENTINEL = -(1 << 63)
 MAX_PROBES = 128
 
+# Geometry of the partitioned insert (csrc/groupby_part.hip): pairs per
+# aggregate tile, slots of its LDS table, largest bucket fan-out.
+PART_TILE_ROWS = _C.GBP_TILE_ROWS if _C is not None else None
+PART_LDS_SLOTS = _C.GBP_LDS_SLOTS if _C is not None else None
+PART_MAX_BUCKETS = _C.GBP_MAX_BUCKETS if _C is not None else None
+
+
+def part_buckets(n: int, nkeys: float, cap: int) -> int:
+    """Bucket fan-out B (a power of two) of the partitioned insert for a
+    batch of n rows over ~nkeys keys.  A tile of T pairs spans at most
+    T/(n/B) + 1 buckets of nkeys/B keys each; B is the smallest fan-out
+    that keeps that count within half the LDS table:
+    T*nkeys/n + nkeys/B <= slots/2.  Clamped to [2, PART_MAX_BUCKETS]
+    and to the table capacity (bucket id = high bits of the slot)."""
+    room = PART_LDS_SLOTS / 2 - PART_TILE_ROWS * nkeys / max(n, 1)
+    b = 2
+    while b < PART_MAX_BUCKETS and (room <= 0 or b * room < nkeys):
+        b <<= 1
+    return min(b, cap)
+
 
 def groupby_supported(keys: torch.Tensor, vals: List[torch.Tensor],
                       aggs: List[str]) -> bool:
@@ -202,10 +222,15 @@ class GroupTable:
         if forced in ("lds", "global"):
             self._sample_forced = forced
             return
+        if forced == "part" and not self._sum_i64:
+            self._sample_forced = "global"  # packed shape only
+            return
         if os.environ.get("BIGSLICE_GB_COMBINE") == "sort":
             self._sample_forced = "sort"
             return
-        self._sample_forced = None
+        # forced "part" still samples: it sizes the table and the bucket
+        # fan-out from the key estimate exactly as the chooser would
+        self._sample_forced = forced if forced == "part" else None
         prefix = min(keys.shape[0], self._CARD_SAMPLE)
         # probe=False: the probe's count readback would sync the
         # stream; the sample must stay fire-and-forget
@@ -226,9 +251,12 @@ class GroupTable:
           insert is 6.2 ms at 10M keys but the sort path stays ~5.1.
         In between (e.g. the north-star consumer shape, ~125 rows/key)
         the streaming insert wins IN CONTEXT (it overlaps with reads;
-        the sort path bunches all work at finish): stay "global"."""
-        if getattr(self, "_sample_forced", None):
-            return self._sample_forced
+        the sort path bunches all work at finish): stay on the
+        streaming insert — "part" (partitioned LDS pre-aggregation)
+        for the int64-sum shape inside _PART_BAND, else "global"."""
+        forced = getattr(self, "_sample_forced", None)
+        if forced and forced != "part":
+            return forced
         distinct = 1 + int(self._sample_ne.item())
         s = self._sample_n
         dbg = os.environ.get("BIGSLICE_GB_DEBUG")
@@ -240,6 +268,7 @@ class GroupTable:
             K = float(distinct)
             for _ in range(20):
                 K = distinct / (1.0 - math.exp(-s / K))
+            self._key_estimate = K
             if self.cap_hint is None:
                 self.cap_hint = _next_pow2(
                     min(max(int(4 * K), 1024), 1 << 30))
@@ -251,12 +280,31 @@ class GroupTable:
             K = max(K, 1.0)
             rows_per_key = self._sample_batch_n / K
             mode = "sort" if rows_per_key > 500 else "global"
+            if (mode == "global" and self._sum_i64
+                    and self._part_band(rows_per_key)):
+                mode = "part"
+        if forced:
+            mode = forced
         if dbg:
             import sys
             print(f"[gb] sample={s} distinct={distinct} "
                   f"cap_hint={self.cap_hint} mode={mode}",
                   file=sys.stderr, flush=True)
         return mode
+
+    # "part" (partitioned LDS pre-aggregation, K19) pays three extra
+    # streaming passes to turn ~rows/key global atomics per key per batch
+    # into one per key per tile; below a few rows per key per batch there
+    # is nothing to absorb.  Batches under _PART_MIN_ROWS take the plain
+    # insert (the passes' fixed cost dominates).
+    _PART_MIN_ROWS = 1 << 21
+    _PART_BAND = (6.0, 500.0)  # rows per key per batch
+    _PART_AUTO = os.environ.get("BIGSLICE_GB_PART", "1") == "1"
+
+    def _part_band(self, rows_per_key: float) -> bool:
+        lo, hi = self._PART_BAND
+        return (self._PART_AUTO and not self._packed
+                and lo <= rows_per_key <= hi)
 
     def insert(self, keys: torch.Tensor, vals: List[torch.Tensor]):
         n = keys.shape[0]
@@ -314,6 +362,12 @@ class GroupTable:
             _C.groupby_insert_lds(keys, vals[0], self.tkeys,
                                   self.tabs[0], self.flags, MAX_PROBES,
                                   1, blocks, dummy)
+        elif (mode == "part" and self._sum_i64
+              and self._PART_MIN_ROWS <= keys.shape[0] < (1 << 31)):
+            nkeys = getattr(self, "_key_estimate", None) or self.cap / 4
+            _C.groupby_insert_part(
+                keys, vals[0], self.tkeys, self.tabs[0], self.flags,
+                MAX_PROBES, part_buckets(keys.shape[0], nkeys, self.cap))
         elif self._lds and mode is None:
             self._insert_adaptive(keys, vals)
         elif (self._sum_i64 and mode == "global"
@@ -490,7 +544,7 @@ class GroupTable:
                 self._alloc(cap)
                 self.batches = []
                 m = getattr(self, "_mode", None)
-                if m not in ("lds", "global"):
+                if m not in ("lds", "global", "part"):
                     m = "global" if self._sort_combinable else None
                 for keys, vals in batches:
                     self._insert_now(keys, vals, m)

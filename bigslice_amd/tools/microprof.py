@@ -44,7 +44,7 @@ def timeit(fn, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("which", choices=["groupby", "groupby_pp",
+    ap.add_argument("which", choices=["groupby", "groupby_pp", "groupby_part",
                                       "insert", "insert_rep",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
@@ -100,6 +100,58 @@ def main():
                 off += c
             t.finish()
         ms = timeit(run, args.iters)
+    elif args.which == "groupby_part":
+        # partitioned LDS pre-aggregation (K19): per-batch kernel times
+        # of histogram+offsets+scatter, of the aggregate pass, and of
+        # the plain one-pass insert over the same batch and warm table
+        n = min(args.rows, int(os.environ.get("PART_BATCH", 8 << 20)))
+        bk, bv = keys[:n].contiguous(), vals[:n].contiguous()
+        cap = args.cap or kernels._next_pow2(4 * args.nkeys)
+        B = int(os.environ.get("PART_BUCKETS", "0")) or \
+            kernels.part_buckets(n, args.nkeys, cap)
+        t = kernels.GroupTable([torch.int64], ["sum"], dev)
+        t._alloc(cap)
+        C = kernels._C
+        pairs, _ = C.groupby_part_scatter(bk, bv, cap, B)
+        out.update(rows=n, cap=cap, buckets=B)
+        out["scatter_ms"] = timeit(
+            lambda: C.groupby_part_scatter(bk, bv, cap, B), args.iters)
+        out["aggregate_ms"] = timeit(
+            lambda: C.groupby_part_aggregate(
+                pairs, t.tkeys, t.tabs[0], t.flags, kernels.MAX_PROBES),
+            args.iters)
+        out["part_ms"] = timeit(
+            lambda: C.groupby_insert_part(
+                bk, bv, t.tkeys, t.tabs[0], t.flags, kernels.MAX_PROBES,
+                B), args.iters)
+        out["plain_ms"] = timeit(
+            lambda: C.groupby_insert(
+                bk, [bv], t.codes, t.tkeys, t.tabs, t.flags,
+                kernels.MAX_PROBES), args.iters)
+        assert int(t.flags[1].item()) == 0, "table overflow"
+        # global atomics of one aggregate pass = rows that missed the
+        # LDS tables + flushed slots; counted on a fresh table as the
+        # sum of a ones column
+        t2 = kernels.GroupTable([torch.int64], ["sum"], dev)
+        t2._alloc(cap)
+        ones = torch.ones_like(pairs)
+        ones[:, 0] = pairs[:, 0]
+        C.groupby_part_aggregate(ones, t2.tkeys, t2.tabs[0], t2.flags,
+                                 kernels.MAX_PROBES)
+        out["distinct_in_batch"] = int((t2.tkeys[:cap]
+                                        != kernels.GB_SENTINEL).sum())
+        # distinct keys per aggregate tile, summed: the flushed slots (a
+        # lower bound on the pass's global atomics; LDS-table misses add
+        # one each)
+        T = kernels.PART_TILE_ROWS
+        full = (n // T) * T
+        tk = pairs[:full, 0].reshape(-1, T).sort(dim=1).values
+        flushed = int((tk[:, 1:] != tk[:, :-1]).sum()) + tk.shape[0]
+        if full < n:
+            flushed += int(pairs[full:, 0].unique().shape[0])
+        out["flushed_slots"] = flushed
+        args.rows = n
+        ms = out["part_ms"]
     elif args.which in ("insert", "insert_rep"):
         # steady-state insert throughput into a presized packed table
         # (all keys present after warmup: pure probe+atomicAdd path);
