@@ -338,10 +338,75 @@ std::tuple<torch::Tensor, torch::Tensor> part_scatter_impl(
   return {pairs, totals};
 }
 
+// Owner pass + cleanup pass over already partitioned pairs (see "Owned
+// slices" in groupby_part.hip).  pairs is reordered in place (spilled
+// rows move to the front of the region their owner consumed).  Returns
+// clean[b]: rows at the front of segment b left to the cleanup pass.
+torch::Tensor part_owned_impl(const torch::Tensor& pairs,
+                              const torch::Tensor& totals,
+                              const torch::Tensor& tkeys,
+                              const torch::Tensor& tab,
+                              const torch::Tensor& flags,
+                              int64_t max_probes) {
+  const int64_t n = pairs.size(0);
+  const int64_t cap = tkeys.size(0) - 1;
+  const int64_t nbuckets = totals.size(0);
+  TORCH_CHECK(n > 0 && n < (int64_t(1) << 31), "1 <= rows < 2^31");
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && cap <= (int64_t(1) << 31),
+              "capacity must be 2^k");
+  TORCH_CHECK(nbuckets >= 2 && nbuckets <= GBP_MAX_BUCKETS &&
+                  (nbuckets & (nbuckets - 1)) == 0 && nbuckets <= cap,
+              "nbuckets must be a power of two in [2, ", GBP_MAX_BUCKETS,
+              "] and at most the capacity");
+  const int64_t S = cap / nbuckets;
+  TORCH_CHECK(S <= GBP_LDS_SLOTS, "owned pass needs capacity / nbuckets <= ",
+              GBP_LDS_SLOTS);
+  TORCH_CHECK(tab.size(0) == cap + 1 && tkeys.is_contiguous() &&
+              tab.is_contiguous());
+  TORCH_CHECK((uintptr_t)tkeys.data_ptr() % 16 == 0 &&
+                  (uintptr_t)tab.data_ptr() % 16 == 0,
+              "table must be 16-byte aligned");
+  uint32_t shift = 0;
+  while ((cap >> shift) > nbuckets) ++shift;
+  const uint32_t nb = (uint32_t)nbuckets;
+  const uint32_t seed = 0x9acb0442u;
+  auto clean = torch::empty({nbuckets}, totals.options());
+  auto todo = torch::empty({nbuckets, 2}, totals.options());
+  auto stream = current_stream();
+  // the static counters put a 4096-slot slice just over the 64 KiB a
+  // kernel gets without asking
+  // (the attribute is per device and cheap to set: no once-flag)
+  HIP_CHECK(hipFuncSetAttribute(
+      (const void*)k_gbp_owned, hipFuncAttributeMaxDynamicSharedMemorySize,
+      16 * GBP_LDS_SLOTS));
+  hipLaunchKernelGGL(k_gbp_owned, dim3(nb), dim3(GBP_THREADS),
+                     (size_t)(16 * S), stream,
+                     (GbPair*)pairs.data_ptr<int64_t>(), n,
+                     (const uint32_t*)totals.data_ptr<int32_t>(), nb,
+                     (uint32_t)S, tkeys.data_ptr<int64_t>(),
+                     (long long*)tab.data_ptr<int64_t>(), seed, max_probes,
+                     (uint32_t*)clean.data_ptr<int32_t>(),
+                     (uint2*)todo.data_ptr<int32_t>());
+  HIP_CHECK(hipGetLastError());
+  const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
+  hipLaunchKernelGGL(k_gbp_cleanup, dim3((uint32_t)ntiles),
+                     dim3(GBP_THREADS), 0, stream,
+                     (const GbPair*)pairs.data_ptr<int64_t>(), n,
+                     tkeys.data_ptr<int64_t>(),
+                     (long long*)tab.data_ptr<int64_t>(), cap, seed,
+                     flags.data_ptr<int32_t>(),
+                     flags.data_ptr<int32_t>() + 1, max_probes,
+                     (const uint2*)todo.data_ptr<int32_t>(), nb, shift);
+  HIP_CHECK(hipGetLastError());
+  return clean;
+}
+
+// owned != 0: bucket-owning aggregate (needs capacity / nbuckets <=
+// GBP_LDS_SLOTS); owned == 0: the tiled aggregate with its global flush.
 void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
                          torch::Tensor tkeys, torch::Tensor tab,
                          torch::Tensor flags, int64_t max_probes,
-                         int64_t nbuckets) {
+                         int64_t nbuckets, int64_t owned) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   TORCH_CHECK(vals.scalar_type() == torch::kInt64 &&
               vals.size(0) == keys.size(0));
@@ -353,6 +418,11 @@ void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
   int64_t cap = tkeys.size(0) - 1;
   auto parts = part_scatter_impl(keys, vals, cap, nbuckets);
   const torch::Tensor& pairs = std::get<0>(parts);
+  if (owned) {
+    part_owned_impl(pairs, std::get<1>(parts), tkeys, tab, flags,
+                    max_probes);
+    return;
+  }
   const uint32_t seed = 0x9acb0442u;
   const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
   hipLaunchKernelGGL(k_gbp_aggregate, dim3((uint32_t)ntiles),
@@ -397,6 +467,21 @@ void groupby_part_aggregate(torch::Tensor pairs, torch::Tensor tkeys,
                      flags.data_ptr<int32_t>(),
                      flags.data_ptr<int32_t>() + 1, max_probes);
   HIP_CHECK(hipGetLastError());
+}
+
+// Owner + cleanup passes alone over already partitioned pairs and their
+// rows per bucket (tests, kernel timing).  Reorders pairs in place;
+// returns clean [nbuckets].
+torch::Tensor groupby_part_owned(torch::Tensor pairs, torch::Tensor totals,
+                                 torch::Tensor tkeys, torch::Tensor tab,
+                                 torch::Tensor flags, int64_t max_probes) {
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt64 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(1) == 2);
+  TORCH_CHECK(totals.is_cuda() && totals.scalar_type() == torch::kInt32 &&
+              totals.is_contiguous() && totals.dim() == 1);
+  TORCH_CHECK(tab.scalar_type() == torch::kInt64);
+  return part_owned_impl(pairs, totals, tkeys, tab, flags, max_probes);
 }
 
 // Multi-row software-pipelined one-level insert (single int64 SUM
@@ -1258,7 +1343,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("groupby_insert_lds", &groupby_insert_lds,
         "two-level LDS+global insert (int64 sum)");
   m.def("groupby_insert_part", &groupby_insert_part,
-        "partitioned LDS pre-aggregating insert (single i64 sum)");
+        "partitioned LDS pre-aggregating insert (single i64 sum)",
+        py::arg("keys"), py::arg("vals"), py::arg("tkeys"), py::arg("tab"),
+        py::arg("flags"), py::arg("max_probes"), py::arg("nbuckets"),
+        py::arg("owned") = 0);
+  m.def("groupby_part_owned", &groupby_part_owned,
+        "owner + cleanup passes of the partitioned insert; returns clean");
+  m.attr("GBP_OWN_LIMIT") = (int64_t)GBP_OWN_LIMIT;
   m.def("groupby_part_scatter", &groupby_part_scatter,
         "bucket scatter of the partitioned insert");
   m.def("groupby_part_aggregate", &groupby_part_aggregate,

@@ -16,6 +16,10 @@
 //   4. k_gbp_aggregate fixed tiles of the partitioned buffer -> LDS hash
 //                     table (LDS CAS + 64-bit LDS add) -> one
 //                     gb_global_insert_sum per occupied LDS slot
+//   4'. k_gbp_owned + k_gbp_cleanup replace 4 when a bucket's table slice
+//                     fits in LDS: its owner updates the slice in LDS and
+//                     stores it back, no global atomics ("Owned slices"
+//                     below)
 //
 // Bucket id = high bits of the global table slot hash, so the rows of a
 // bucket also share a table range.  The global table, its probing, the
@@ -242,33 +246,85 @@ __device__ __forceinline__ bool gbp_lds_add(long long k, long long v,
 // Grid = ceil(n / GBP_TILE_ROWS) over fixed tiles of the partitioned
 // buffer: a tile may span bucket boundaries and a skewed bucket spans
 // many tiles, so no workgroup's work depends on the key distribution.
-extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_aggregate(
+//
+// CLEAN: the pass after k_gbp_owned.  todo[b] = (start, end) of the rows
+// of bucket b that are still to be inserted (the front of its segment:
+// what the owner did not reach plus what it spilled), so only rows i
+// with i < end[bucket(i)] are live.  The tile works on [first, last), the
+// hull of the intervals it meets: empty, it exits before it reads a pair
+// or touches its LDS table; at most one row per thread (the usual case:
+// a few spilled rows at the start of a segment), the rows go straight to
+// the global table.
+template <bool CLEAN>
+__device__ __forceinline__ void gbp_aggregate_tile(
     const GbPair* pairs, int64_t n, int64_t* tkeys, long long* tab,
     int64_t cap, uint32_t seed, int32_t* sentinel_seen, int32_t* overflow,
-    int64_t max_probes) {
+    int64_t max_probes, const uint2* todo, uint32_t nb, uint32_t shift) {
   __shared__ long long lk[GBP_LDS_SLOTS];
   __shared__ long long lv[GBP_LDS_SLOTS];
+  // CLEAN only; unused in k_gbp_aggregate, where the compiler drops them
+  // (its LDS stays 65536 B in the kernel-resource-usage remark)
+  __shared__ uint32_t lend[CLEAN ? GBP_MAX_BUCKETS : 1];
+  __shared__ uint32_t hull[2];
+  const uint64_t gmask = (uint64_t)cap - 1;
+  const int64_t base = (int64_t)blockIdx.x * GBP_TILE_ROWS;
+  int64_t first = base, last = n;
+  if constexpr (CLEAN) {
+    const uint32_t t0 = (uint32_t)base;  // n < 2^31
+    const uint32_t t1 = (uint32_t)min(base + GBP_TILE_ROWS, n);
+    if (threadIdx.x == 0) {
+      hull[0] = t1;
+      hull[1] = t0;
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) {
+      const uint2 se = todo[b];
+      lend[b] = se.y;
+      if (se.y > se.x && se.x < t1 && se.y > t0) {
+        atomicMin(&hull[0], max(se.x, t0));
+        atomicMax(&hull[1], min(se.y, t1));
+      }
+    }
+    __syncthreads();
+    first = hull[0];
+    last = hull[1];
+    if (first >= last) return;
+    if (last - first <= GBP_THREADS) {
+      const int64_t i = first + threadIdx.x;
+      if (i < last) {
+        const GbPair pr = pairs[i];
+        if (i < (int64_t)lend[gbp_bucket(pr.k, seed, (uint32_t)gmask, shift)])
+          gb_global_insert_sum(pr.k, pr.v, tkeys, tab, gmask, cap, seed,
+                               sentinel_seen, overflow, max_probes);
+      }
+      return;
+    }
+  }
   for (int s = threadIdx.x; s < GBP_LDS_SLOTS; s += GBP_THREADS) {
     lk[s] = GB_SENTINEL;
     lv[s] = 0;
   }
   __syncthreads();
-  const uint64_t gmask = (uint64_t)cap - 1;
-  const int64_t base = (int64_t)blockIdx.x * GBP_TILE_ROWS;
   // G loads in flight per thread before the first LDS probe
   constexpr int G = 8;
   for (int j0 = 0; j0 < GBP_TILE_ROWS / GBP_THREADS; j0 += G) {
+    if (CLEAN && first + j0 * GBP_THREADS >= last) break;
     GbPair pr[G];
 #pragma unroll
     for (int j = 0; j < G; ++j) {
-      const int64_t i = base + (j0 + j) * GBP_THREADS + threadIdx.x;
-      if (i < n) pr[j] = pairs[i];
+      const int64_t i = first + (j0 + j) * GBP_THREADS + threadIdx.x;
+      if (i < last) pr[j] = pairs[i];
     }
 #pragma unroll
     for (int j = 0; j < G; ++j) {
-      const int64_t i = base + (j0 + j) * GBP_THREADS + threadIdx.x;
-      if (i < n && (pr[j].k == GB_SENTINEL ||
-                    !gbp_lds_add(pr[j].k, pr[j].v, lk, lv, seed)))
+      const int64_t i = first + (j0 + j) * GBP_THREADS + threadIdx.x;
+      bool live = i < last;
+      if constexpr (CLEAN)
+        live = live &&
+               i < (int64_t)lend[gbp_bucket(pr[j].k, seed, (uint32_t)gmask,
+                                            shift)];
+      if (live && (pr[j].k == GB_SENTINEL ||
+                   !gbp_lds_add(pr[j].k, pr[j].v, lk, lv, seed)))
         gb_global_insert_sum(pr[j].k, pr[j].v, tkeys, tab, gmask, cap, seed,
                              sentinel_seen, overflow, max_probes);
     }
@@ -280,4 +336,194 @@ extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_aggregate(
       gb_global_insert_sum(k, lv[s], tkeys, tab, gmask, cap, seed,
                            sentinel_seen, overflow, max_probes);
   }
+}
+
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_aggregate(
+    const GbPair* pairs, int64_t n, int64_t* tkeys, long long* tab,
+    int64_t cap, uint32_t seed, int32_t* sentinel_seen, int32_t* overflow,
+    int64_t max_probes) {
+  gbp_aggregate_tile<false>(pairs, n, tkeys, tab, cap, seed, sentinel_seen,
+                            overflow, max_probes, nullptr, 0, 0);
+}
+
+// ---------------------------------------------------------------------
+// Owned slices.  Bucket b is the table range [b*S, (b+1)*S), S = cap / B.
+// When S slots fit in LDS, the workgroup that owns bucket b loads that
+// slice of the REAL table, runs the table's own linear probe on it with
+// LDS atomics and stores it back with plain stores: no global atomic.
+//
+//   k_gbp_owned    grid = B.  At most GBP_OWN_LIMIT rows from the tail of
+//                  segment b, so a heavy bucket costs its owner no more
+//                  than a light one.  Rows it cannot place are compacted
+//                  to the front of the region it consumed; clean[b] =
+//                  rows of segment b, counted from its start, that are
+//                  still to be inserted, todo[b] = that interval.
+//   k_gbp_cleanup  the tiled aggregate above restricted to those
+//                  intervals: the only global atomics left.
+//
+// Plain stores to a slice happen only in k_gbp_owned, by its owner;
+// whatever may touch a foreign slice (a chain that leaves the range,
+// the sentinel slot at cap, the rest of an oversize bucket) waits for
+// the next launch, so no write-back races an atomic.
+//
+// A key lands in the slot gb_global_insert_sum would have chosen: the
+// probe starts at slot_hash & (S-1) of the slice, walks linearly, claims
+// the first empty slot, and gives up after max_probes slots.  A chain
+// that reaches the end of the slice is spilled, not wrapped (for the
+// last slice that is the table's wrap to slot 0).  The table never
+// deletes, so a key that once spilled past its slice end and was stored
+// in a later slice still finds every slot from its home to the slice end
+// taken, and spills again: it is never stored twice.
+#define GBP_OWN_LIMIT (2 * GBP_TILE_ROWS)
+#define GBP_OWN_G 8
+#define GBP_OWN_CHUNK (GBP_OWN_G * GBP_THREADS)
+
+// One row through the owned slice; false = spill.  *won is set when the
+// row claimed an empty slot.
+__device__ __forceinline__ bool gbp_own_add(long long k, long long v,
+                                            uint32_t l, long long* lk,
+                                            long long* lv, uint32_t S,
+                                            uint32_t max_probes,
+                                            bool* won) {
+  for (uint32_t p = 0;;) {
+    long long cur = lk[l];
+    if (cur == GB_SENTINEL) {
+      const long long prev = atomicCAS((unsigned long long*)&lk[l],
+                                       (unsigned long long)GB_SENTINEL,
+                                       (unsigned long long)k);
+      if (prev == GB_SENTINEL) *won = true;
+      cur = (prev == GB_SENTINEL) ? k : prev;
+    }
+    if (cur == k) {
+      atomicAdd((unsigned long long*)&lv[l], (unsigned long long)v);
+      return true;
+    }
+    if (++l == S || ++p >= max_probes) return false;
+  }
+}
+
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_owned(
+    GbPair* pairs, int64_t n, const uint32_t* totals, uint32_t nb,
+    uint32_t S, int64_t* tkeys, long long* tab, uint32_t seed,
+    int64_t max_probes, uint32_t* clean, uint2* todo) {
+  extern __shared__ longlong2 gbp_own_lds[];  // S keys, then S sums
+  __shared__ uint32_t seg[GBP_MAX_BUCKETS];
+  __shared__ uint32_t wtmp[GBP_THREADS / 64];
+  __shared__ uint32_t lwon, nspill;
+  long long* lk = (long long*)gbp_own_lds;
+  long long* lv = lk + S;
+  const uint32_t b = blockIdx.x;
+  const uint32_t total = totals[b];
+  if (total == 0) {  // the slice stays untouched
+    if (threadIdx.x == 0) {
+      clean[b] = 0;
+      todo[b] = make_uint2(0, 0);
+    }
+    return;
+  }
+  for (uint32_t i = threadIdx.x; i < nb; i += GBP_THREADS)
+    seg[i] = totals[i];
+  if (threadIdx.x == 0) {
+    lwon = 0;
+    nspill = 0;
+  }
+  __syncthreads();
+  gbp_block_scan(seg, nb, wtmp);
+  const uint32_t proc = min(total, (uint32_t)GBP_OWN_LIMIT);
+  const uint32_t start = seg[b];
+  const uint32_t p0 = start + (total - proc);  // processed: [p0, p0+proc)
+
+  GbPair buf[2][GBP_OWN_G];  // chunk c in buf[c & 1], c + 1 in flight
+#pragma unroll
+  for (int j = 0; j < GBP_OWN_G; ++j) {
+    const uint32_t r = j * GBP_THREADS + threadIdx.x;
+    if (r < proc && (int64_t)p0 + r < n) buf[0][j] = pairs[p0 + r];
+  }
+
+  const int64_t s0 = (int64_t)b * S;
+  if (S >= 2) {
+    const longlong2* gk = (const longlong2*)(tkeys + s0);
+    const longlong2* gv = (const longlong2*)(tab + s0);
+#pragma unroll 4
+    for (uint32_t i = threadIdx.x; i < S / 2; i += GBP_THREADS) {
+      ((longlong2*)lk)[i] = gk[i];
+      ((longlong2*)lv)[i] = gv[i];
+    }
+  } else if (threadIdx.x == 0) {
+    lk[0] = tkeys[s0];
+    lv[0] = tab[s0];
+  }
+
+  const uint32_t maxp =
+      (uint32_t)min(max_probes, (int64_t)GBP_LDS_SLOTS);  // S <= slots
+  bool won = false;
+  // A chunk's spills go to the front of the processed region.  Their
+  // count never exceeds the rows of the chunks loaded so far, so a spill
+  // never lands on a pair that is still to be read, PROVIDED a chunk's
+  // loads are ordered before the other threads' later stores.  Every
+  // thread issues the loads of chunk c before the barrier of chunk c and
+  // stores spills only after it.  The ordering comes from the workgroup
+  // fence that __syncthreads() carries: it keeps the compiler from
+  // sinking the loads below the barrier, and the hardware performs a
+  // workgroup's loads and stores through one CU in issue order.  A bare
+  // __builtin_amdgcn_s_barrier() has no fence and would not be enough.
+#pragma unroll
+  for (int c = 0; c < GBP_OWN_LIMIT / GBP_OWN_CHUNK; ++c) {
+    if ((uint32_t)c * GBP_OWN_CHUNK < proc) {  // uniform
+      __syncthreads();  // first chunk: also the slice is in LDS
+      if ((uint32_t)(c + 1) * GBP_OWN_CHUNK < proc) {
+#pragma unroll
+        for (int j = 0; j < GBP_OWN_G; ++j) {
+          const uint32_t r =
+              (c + 1) * GBP_OWN_CHUNK + j * GBP_THREADS + threadIdx.x;
+          if (r < proc && (int64_t)p0 + r < n)
+            buf[(c + 1) & 1][j] = pairs[p0 + r];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < GBP_OWN_G; ++j) {
+        const uint32_t r = c * GBP_OWN_CHUNK + j * GBP_THREADS + threadIdx.x;
+        if (r < proc && (int64_t)p0 + r < n) {
+          const GbPair pr = buf[c & 1][j];
+          const long long k = pr.k;
+          const bool placed =
+              k != GB_SENTINEL &&
+              gbp_own_add(k, pr.v, mm3_u64((uint64_t)k, seed) & (S - 1),
+                          lk, lv, S, maxp, &won);
+          if (!placed) {
+            const uint32_t d = p0 + atomicAdd(&nspill, 1u);
+            if (d < n) pairs[d] = pr;  // always true, as in the scatter
+          }
+        }
+      }
+    }
+  }
+  if (won) lwon = 1;
+  __syncthreads();
+
+  if (S >= 2) {
+    longlong2* gk = (longlong2*)(tkeys + s0);
+    longlong2* gv = (longlong2*)(tab + s0);
+    const bool keys_too = lwon != 0;  // no new key: the keys are unchanged
+    for (uint32_t i = threadIdx.x; i < S / 2; i += GBP_THREADS) {
+      gv[i] = ((const longlong2*)lv)[i];
+      if (keys_too) gk[i] = ((const longlong2*)lk)[i];
+    }
+  } else if (threadIdx.x == 0) {
+    tab[s0] = lv[0];
+    if (lwon) tkeys[s0] = lk[0];
+  }
+  if (threadIdx.x == 0) {
+    const uint32_t c = (total - proc) + nspill;
+    clean[b] = c;
+    todo[b] = make_uint2(start, start + c);
+  }
+}
+
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_cleanup(
+    const GbPair* pairs, int64_t n, int64_t* tkeys, long long* tab,
+    int64_t cap, uint32_t seed, int32_t* sentinel_seen, int32_t* overflow,
+    int64_t max_probes, const uint2* todo, uint32_t nb, uint32_t shift) {
+  gbp_aggregate_tile<true>(pairs, n, tkeys, tab, cap, seed, sentinel_seen,
+                           overflow, max_probes, todo, nb, shift);
 }

@@ -117,6 +117,33 @@ def part_buckets(n: int, nkeys: float, cap: int) -> int:
     return min(b, cap)
 
 
+# Rows an owner workgroup of the bucket-owning aggregate takes from its
+# segment; the rest of an oversize bucket goes to the tiled cleanup pass.
+PART_OWN_LIMIT = _C.GBP_OWN_LIMIT if _C is not None else None
+
+
+def part_owned_buckets(n: int, cap: int, lds_slots: int, tile_rows: int,
+                       max_buckets: int):
+    """(B, S) of the bucket-owning aggregate pass for n rows into a table
+    of cap slots, or None when it does not apply.  A workgroup owns the
+    table slice of one bucket, S = cap / B slots, in LDS, so S must not
+    exceed lds_slots; and there should be about as many workgroups as
+    the tiled pass has tiles, to fill the chip.  B is the smallest power
+    of two >= max(cap / lds_slots, n / tile_rows), clamped to
+    [2, min(max_buckets, cap)]."""
+    want = max(cap / lds_slots, n / tile_rows)
+    b = 2
+    while b < want:
+        b <<= 1
+    b = max(2, min(b, max_buckets, cap))
+    s = cap // b
+    return (b, s) if s <= lds_slots else None
+
+
+def _part_owned_enabled() -> bool:
+    return os.environ.get("BIGSLICE_GB_PART_OWNED", "1") == "1"
+
+
 def groupby_supported(keys: torch.Tensor, vals: List[torch.Tensor],
                       aggs: List[str]) -> bool:
     if _C is None:
@@ -364,10 +391,19 @@ class GroupTable:
                                   1, blocks, dummy)
         elif (mode == "part" and self._sum_i64
               and self._PART_MIN_ROWS <= keys.shape[0] < (1 << 31)):
-            nkeys = getattr(self, "_key_estimate", None) or self.cap / 4
-            _C.groupby_insert_part(
-                keys, vals[0], self.tkeys, self.tabs[0], self.flags,
-                MAX_PROBES, part_buckets(keys.shape[0], nkeys, self.cap))
+            own = part_owned_buckets(
+                keys.shape[0], self.cap, PART_LDS_SLOTS, PART_TILE_ROWS,
+                PART_MAX_BUCKETS) if _part_owned_enabled() else None
+            if own is not None:
+                _C.groupby_insert_part(
+                    keys, vals[0], self.tkeys, self.tabs[0], self.flags,
+                    MAX_PROBES, own[0], 1)
+            else:
+                nkeys = getattr(self, "_key_estimate", None) or self.cap / 4
+                _C.groupby_insert_part(
+                    keys, vals[0], self.tkeys, self.tabs[0], self.flags,
+                    MAX_PROBES,
+                    part_buckets(keys.shape[0], nkeys, self.cap))
         elif self._lds and mode is None:
             self._insert_adaptive(keys, vals)
         elif (self._sum_i64 and mode == "global"

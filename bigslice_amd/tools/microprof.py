@@ -128,6 +128,32 @@ def main():
             lambda: C.groupby_insert(
                 bk, [bv], t.codes, t.tkeys, t.tabs, t.flags,
                 kernels.MAX_PROBES), args.iters)
+        # bucket-owning aggregate (owner + cleanup passes) at its own
+        # fan-out, against the tiled aggregate above
+        own = kernels.part_owned_buckets(
+            n, cap, kernels.PART_LDS_SLOTS, kernels.PART_TILE_ROWS,
+            kernels.PART_MAX_BUCKETS)
+        if own is not None:
+            Bo = own[0]
+            out["owned_buckets"], out["owned_slice"] = own
+            out["owned_scatter_ms"] = timeit(
+                lambda: C.groupby_part_scatter(bk, bv, cap, Bo), args.iters)
+            po, to = C.groupby_part_scatter(bk, bv, cap, Bo)
+            # rows the owners leave to the cleanup pass: an upper bound
+            # on the global atomics that remain.  Taken on the first run
+            # (spilled rows overwrite consumed ones, so the buffer is
+            # good for timing afterwards, not for results)
+            clean = C.groupby_part_owned(po, to, t.tkeys, t.tabs[0],
+                                         t.flags, kernels.MAX_PROBES)
+            out["cleanup_rows"] = int(clean.sum())
+            out["owned_aggregate_ms"] = timeit(
+                lambda: C.groupby_part_owned(
+                    po, to, t.tkeys, t.tabs[0], t.flags,
+                    kernels.MAX_PROBES), args.iters)
+            out["owned_part_ms"] = timeit(
+                lambda: C.groupby_insert_part(
+                    bk, bv, t.tkeys, t.tabs[0], t.flags,
+                    kernels.MAX_PROBES, Bo, 1), args.iters)
         assert int(t.flags[1].item()) == 0, "table overflow"
         # global atomics of one aggregate pass = rows that missed the
         # LDS tables + flushed slots; counted on a fresh table as the
