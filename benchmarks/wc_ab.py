@@ -1,5 +1,7 @@
-"""Wordcount A/B on device: host string-keyed Reduce vs gpu_wordcount
-(K17 device dictionary ids + device count)."""
+"""Wordcount A/B on device: host string-keyed Reduce vs a BYTES column
+packed from host tokens vs gpu_wordcount (K17 device dictionary ids +
+device count) vs device_wordcount (K20 device tokenizer feeding the
+device string-keyed Reduce)."""
 import sys, time
 sys.path.insert(0, ".")
 import bigslice_amd as bs
@@ -54,10 +56,22 @@ def bytes_path():
     return out
 
 
+def device_split_path():
+    """recipes.device_wordcount: lines pack into a BytesColumn per
+    batch and are split on the device; no per-word Python anywhere."""
+    fv = bs.func(lambda nshard, token: recipes.device_wordcount(
+        nshard, lambda: iter(lines)))
+    res = sess.run(fv, 4, 0)
+    out = {k.decode(): v for k, v in res.scan()}
+    res.discard()
+    return out
+
+
 for name, fn in (("host-string", host_path),
                  ("bytes-col", bytes_path),
                  ("gpu-dict", lambda: recipes.gpu_wordcount(
-                     sess, 4, lines, dev))):
+                     sess, 4, lines, dev)),
+                 ("device-split", device_split_path)):
     got = fn()
     assert got == dict(ref), name
     t0 = time.perf_counter()

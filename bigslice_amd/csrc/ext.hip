@@ -23,6 +23,7 @@
 #include "vecagg.hip"
 #include "strings.hip"
 #include "expr.hip"
+#include "tokenize.hip"
 
 namespace {
 
@@ -1330,6 +1331,74 @@ std::vector<torch::Tensor> expr_apply(
   return outs;
 }
 
+// K20: split the rows of a compacted BYTES column into tokens
+// (tokenize.hip).  data must be zero-based and contiguous under offsets
+// (offsets[0] == 0, offsets[n] == data.size(0)); mask4 is the 256-bit
+// delimiter set.  Returns (out_data, out_offsets[, tok_row]), sized
+// exactly after ONE readback of the two totals.
+std::vector<torch::Tensor> tokenize_bytes(torch::Tensor data,
+                                          torch::Tensor offsets,
+                                          std::vector<uint64_t> mask4,
+                                          bool with_rows) {
+  TORCH_CHECK(data.is_cuda() && data.is_contiguous() && data.dim() == 1 &&
+              data.scalar_type() == torch::kUInt8,
+              "tokenize_bytes: contiguous uint8 device data required");
+  TORCH_CHECK(offsets.is_cuda() && offsets.is_contiguous() &&
+              offsets.dim() == 1 && offsets.size(0) >= 1 &&
+              offsets.scalar_type() == torch::kInt64,
+              "tokenize_bytes: contiguous int64 device offsets required");
+  TORCH_CHECK(mask4.size() == 4, "tokenize_bytes: mask4 has 4 words");
+  const int64_t total = data.size(0);
+  const int64_t n = offsets.size(0) - 1;
+  TORCH_CHECK(total < (1ll << 31),
+              "tokenize_bytes: total bytes must be below 2^31");
+  TORCH_CHECK(n > 0 || total == 0, "tokenize_bytes: bytes without rows");
+  auto i64 = offsets.options();
+  if (total == 0) {
+    std::vector<torch::Tensor> out = {torch::empty({0}, data.options()),
+                                      torch::zeros({1}, i64)};
+    if (with_rows) out.push_back(torch::empty({0}, i64));
+    return out;
+  }
+  // the kernels read the text with 16-byte loads
+  if (((uintptr_t)data.data_ptr<uint8_t>() & 15) != 0) data = data.clone();
+  const TokMask m{mask4[0], mask4[1], mask4[2], mask4[3]};
+  auto stream = current_stream();
+  const int64_t ntiles = (total + TOK_TILE - 1) / TOK_TILE;
+  auto counts = torch::empty({ntiles, 2}, i64.dtype(torch::kInt32));
+  hipLaunchKernelGGL(k_tok_count, dim3((int)ntiles), dim3(TOK_BLOCK), 0,
+                     stream, data.data_ptr<uint8_t>(), total,
+                     offsets.data_ptr<int64_t>(), n, m,
+                     (unsigned int*)counts.data_ptr<int32_t>());
+  HIP_CHECK(hipGetLastError());
+  // Scan both counters at once: a tile's uint32 pair is one int64
+  // (kept in the low word), and neither sum reaches 2^31, so the low
+  // word never carries into the high one.  (A [tiles, 2] cumsum over
+  // dim 0 takes torch's strided outer-dim scan: measured 569 us for
+  // 4096 tiles, against 83 us for the two kernels.)
+  auto incl = at::cumsum(counts.view(torch::kInt64).flatten(), 0);
+  // the one host readback
+  const uint64_t totals = (uint64_t)incl[ntiles - 1].item<int64_t>();
+  const int64_t nkept = (int64_t)(totals & 0xFFFFFFFFull);
+  const int64_t ntok = (int64_t)(totals >> 32);
+  auto out_data = torch::empty({nkept}, data.options());
+  auto out_offsets = torch::empty({ntok + 1}, i64);
+  torch::Tensor tok_row;
+  if (with_rows) tok_row = torch::empty({ntok}, i64);
+  hipLaunchKernelGGL(k_tok_write, dim3((int)ntiles), dim3(TOK_BLOCK), 0,
+                     stream, data.data_ptr<uint8_t>(), total,
+                     offsets.data_ptr<int64_t>(), n, m,
+                     (const unsigned int*)incl.data_ptr<int64_t>(), nkept,
+                     ntok,
+                     out_data.data_ptr<uint8_t>(),
+                     out_offsets.data_ptr<int64_t>(),
+                     with_rows ? tok_row.data_ptr<int64_t>() : nullptr);
+  HIP_CHECK(hipGetLastError());
+  std::vector<torch::Tensor> out = {out_data, out_offsets};
+  if (with_rows) out.push_back(tok_row);
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1394,4 +1463,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("slot_pids", &slot_pids, "table-slot-range partition ids");
   m.def("expr_apply", &expr_apply,
         "fused Map/Filter expression interpreter (K13)");
+  m.def("tokenize_bytes", &tokenize_bytes,
+        "split BYTES rows into tokens on a delimiter set (K20)");
+  m.attr("TOKENIZE_TILE_BYTES") = (int64_t)TOK_TILE;
 }

@@ -99,6 +99,17 @@ class BytesColumn:
             torch.from_numpy(data).to(device),
             torch.from_numpy(offsets).to(device))
 
+    @staticmethod
+    def from_buffer(buf, device: str = "cpu") -> "BytesColumn":
+        """A one-row column over a whole bytes-like object (a text chunk
+        read from a file, say).  split() then tokenizes it with no
+        per-line Python: the default delimiter set contains newline."""
+        import numpy as np
+        data = np.frombuffer(buf, dtype=np.uint8).copy()
+        offsets = torch.tensor([0, data.shape[0]], dtype=torch.int64)
+        return BytesColumn(torch.from_numpy(data).to(device),
+                           offsets.to(device))
+
     def __len__(self):
         return self.offsets.shape[0] - 1
 
@@ -211,8 +222,72 @@ class BytesColumn:
         offs = c.offsets.cpu().tolist()
         return [data[offs[i]:offs[i + 1]] for i in range(len(c))]
 
+    def split(self, delims=None, with_rows: bool = False):
+        """Split every row into tokens: maximal runs of non-delimiter
+        bytes inside one row (a row boundary always ends a token; empty
+        tokens do not exist).  Returns the token column, or with_rows
+        (tokens, rows) where rows[k] is the index of the source row of
+        token k.
 
-Column = Union[torch.Tensor, list, SegmentedColumn, BytesColumn]
+        delims is a bytes object whose bytes form the delimiter set;
+        None means ASCII whitespace b" \\t\\n\\r\\x0b\\x0c", which makes
+        this bytes.split() per row — not str.split(), which also splits
+        on Unicode spaces.  Bytes 0x80-0xFF are ordinary data unless
+        they are in the set.  An empty set raises ValueError.
+
+        A device column runs the K20 HIP kernels (csrc/tokenize.hip);
+        a host column, or one of 2^31 bytes or more, runs split_torch.
+        Both give identical data, offsets and rows."""
+        from . import kernels
+        mask4 = kernels.tokenize_mask(delims)
+        c = self.compacted()
+        if c.data.is_cuda and c.data.numel() < (1 << 31) and (
+                kernels.have_extension() or not kernels.ALLOW_FALLBACK):
+            out = kernels.tokenize_bytes(c.data, c.offsets.contiguous(),
+                                         mask4, with_rows)
+        else:
+            out = split_torch(c.data, c.offsets, mask4, with_rows)
+        col = BytesColumn(out[0], out[1])
+        return (col, out[2]) if with_rows else col
+
+
+def split_torch(data: torch.Tensor, offsets: torch.Tensor, mask4,
+                with_rows: bool = False):
+    """BytesColumn.split over (data, zero-based offsets) in torch ops,
+    on whatever device the tensors live: delimiter lookup table, shifted
+    kept mask, row-start marks by scatter, cumsum, nonzero.  The CPU
+    path, the fallback past 2^31 bytes, and the A/B baseline of the
+    kernels.  Returns (out_data, out_offsets[, tok_row])."""
+    dev = data.device
+    total = data.shape[0]
+    n = offsets.shape[0] - 1
+    if total == 0:
+        out = (torch.empty(0, dtype=torch.uint8, device=dev),
+               torch.zeros(1, dtype=torch.int64, device=dev))
+        return out + (torch.empty(0, dtype=torch.int64, device=dev),) \
+            if with_rows else out
+    lut = torch.tensor(
+        [not (mask4[b >> 6] >> (b & 63)) & 1 for b in range(256)],
+        dtype=torch.bool).to(dev)
+    keep = lut.index_select(0, data.to(torch.int32))
+    row_start = torch.zeros(total, dtype=torch.bool, device=dev)
+    starts = offsets[:n]
+    row_start[starts[starts < total]] = True
+    prev_keep = torch.zeros_like(keep)
+    prev_keep[1:] = keep[:-1]
+    pos = (keep & (~prev_keep | row_start)).nonzero().flatten()
+    rank = torch.cumsum(keep, 0)  # inclusive rank among kept bytes
+    out_offsets = torch.empty(pos.shape[0] + 1, dtype=torch.int64,
+                              device=dev)
+    out_offsets[:-1] = rank[pos] - 1
+    out_offsets[-1:] = rank[-1:]
+    out = (data[keep], out_offsets)
+    if with_rows:
+        out += (torch.searchsorted(offsets, pos, right=True) - 1,)
+    return out
+
+
+Column =Union[torch.Tensor, list, SegmentedColumn, BytesColumn]
 
 
 def _col_len(col: Column) -> int:

@@ -713,3 +713,41 @@ def expr_apply(program, cols):
     res = iter(got)
     return ([next(res) if kind == "reg" else cols[v]
              for kind, v in program.outputs], count)
+
+
+# -- device tokenizer (K20) --------------------------------------------------
+
+# bytes per tile of the tokenizer kernels (csrc/tokenize.hip)
+TOKENIZE_TILE_BYTES = _C.TOKENIZE_TILE_BYTES if _C is not None else 16384
+
+# bytes.split()'s whitespace (ASCII only; str.split() also splits on
+# Unicode spaces, which this set does not contain)
+ASCII_WHITESPACE = b" \t\n\r\x0b\x0c"
+
+
+def tokenize_mask(delims=None) -> List[int]:
+    """The 256-bit delimiter set as four uint64 words: bit (b & 63) of
+    word (b >> 6) is set iff byte b is a delimiter.  None means ASCII
+    whitespace; an empty set raises ValueError."""
+    if delims is None:
+        delims = ASCII_WHITESPACE
+    if isinstance(delims, str):
+        raise TypeError("delims must be bytes, not str")
+    delims = bytes(delims)
+    if not delims:
+        raise ValueError("empty delimiter set")
+    words = [0, 0, 0, 0]
+    for b in delims:
+        words[b >> 6] |= 1 << (b & 63)
+    return words
+
+
+def tokenize_bytes(data: torch.Tensor, offsets: torch.Tensor, mask4,
+                   with_rows: bool = False):
+    """Split the rows of a compacted device BYTES column (zero-based
+    offsets, data.numel() == offsets[-1] < 2^31) into tokens on the HIP
+    kernels.  Returns (out_data, out_offsets) or, with_rows,
+    (out_data, out_offsets, tok_row).  One host readback (the totals)."""
+    _require("tokenize_bytes")
+    return tuple(_C.tokenize_bytes(data, offsets, list(mask4),
+                                   bool(with_rows)))

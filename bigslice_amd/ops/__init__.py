@@ -4,7 +4,7 @@ from .slice_base import (Dep, Name, Pragma, Slice, TaskContext,  # noqa
                          exclusive, materialize, procs, unwrap)
 from .sources import Const, ReaderFunc, ScanReader  # noqa
 from .elementwise import (Filter, Flatmap, Head, Map, Prefixed, Scan,  # noqa
-                          WriterFunc, schema_of)
+                          Tokenize, WriterFunc, schema_of)
 from .shuffle import Repartition, Reshard, Reshuffle  # noqa
 from .reduce import Fold, Reduce  # noqa
 from .cogroup import Cogroup  # noqa

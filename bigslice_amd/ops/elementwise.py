@@ -1,5 +1,5 @@
-"""Elementwise/pipelined operators: Map, Filter, Flatmap, Head, Scan,
-WriterFunc, Prefixed.
+"""Elementwise/pipelined operators: Map, Filter, Flatmap, Tokenize, Head,
+Scan, WriterFunc, Prefixed.
 
 Role-parity: slice.go:566-637 (Map), :657-725 (Filter), :745-841 (Flatmap),
 :966-994 (Head), :1005-1032 (Scan), :443-548 (WriterFunc), :1044-1071
@@ -19,8 +19,8 @@ from typing import Callable, List, Optional
 
 import torch
 
-from ..frame import Frame
-from ..schema import OBJECT, Schema, is_object
+from ..frame import BytesColumn, Frame
+from ..schema import BYTES, OBJECT, Schema, is_object
 from ..sliceio import IterReader, Reader
 from .slice_base import Dep, Name, Slice, TaskContext
 
@@ -66,7 +66,7 @@ def _normalize_out(res, device_hint: str) -> List:
     if isinstance(res, (tuple, list)):
         out = []
         for c in res:
-            if isinstance(c, torch.Tensor) or isinstance(c, list):
+            if isinstance(c, (torch.Tensor, list, BytesColumn)):
                 out.append(c)
             elif isinstance(c, (int, float, bool)):
                 raise TypeError(
@@ -84,7 +84,8 @@ def _infer_schema_vectorized(fn, in_schema: Schema, prefix: int) -> Optional[Sch
         empty = Frame.empty(in_schema)
         res = fn(*empty.columns)
         cols = _normalize_out(res, "cpu")
-        dts = [c.dtype if isinstance(c, torch.Tensor) else OBJECT
+        dts = [c.dtype if isinstance(c, torch.Tensor) else
+               BYTES if isinstance(c, BytesColumn) else OBJECT
                for c in cols]
         return Schema(dts, min(prefix, len(dts)) or None)
     except Exception:
@@ -293,6 +294,69 @@ class Flatmap(_PipelinedSlice):
         return IterReader(gen())
 
 
+class Tokenize(_PipelinedSlice):
+    """Split column ``col`` (BYTES, or OBJECT rows of str/bytes as
+    ScanReader produces) into tokens: a Flatmap specialised to this one
+    job, with the split running on the device (BytesColumn.split, the
+    K20 kernels).  Each input row yields one output row per token; the
+    output schema is the input schema with column ``col`` replaced by
+    BYTES, every other column repeated per token of its row.  delims as
+    BytesColumn.split: None is ASCII whitespace (bytes.split(), not
+    str.split())."""
+
+    def __init__(self, dep: Slice, col: int = 0, delims=None,
+                 prefix: int = None):
+        in_schema = dep.schema
+        if not (0 <= col < in_schema.num_columns):
+            raise TypeError(f"Tokenize: no column {col}")
+        dt = in_schema.dtypes[col]
+        if not (dt == BYTES or is_object(dt)):
+            raise TypeError(
+                f"Tokenize: column {col} is {dt}, not BYTES or OBJECT")
+        from ..kernels import tokenize_mask
+        tokenize_mask(delims)  # validate at graph-build time
+        self.col = col
+        self.delims = delims
+        dts = list(in_schema.dtypes)
+        dts[col] = BYTES
+        schema = Schema(dts, in_schema.prefix)
+        if prefix is not None:
+            schema = schema.with_prefix(prefix)
+        super().__init__(dep, schema, "tokenize")
+
+    def reader(self, shard, dep_readers, ctx: TaskContext) -> Reader:
+        src = dep_readers[0]
+        col, delims, schema = self.col, self.delims, self.schema
+        with_rows = schema.num_columns > 1
+
+        def gen():
+            for f in src:
+                text = f.columns[col]
+                if not isinstance(text, BytesColumn):
+                    text = BytesColumn.from_list(text)
+                if ctx.device != "cpu" and not text.data.is_cuda:
+                    text = text.to(ctx.device, non_blocking=True)
+                out = text.split(delims, with_rows)
+                toks, rows = out if with_rows else (out, None)
+                if not len(toks):
+                    continue
+                cols: List = []
+                host_rows = None
+                for i, c in enumerate(f.columns):
+                    if i == col:
+                        cols.append(toks)
+                    elif isinstance(c, torch.Tensor):
+                        cols.append(c[rows.to(c.device)])
+                    elif isinstance(c, BytesColumn):
+                        cols.append(c.select(rows))
+                    else:
+                        if host_rows is None:
+                            host_rows = rows.cpu().tolist()
+                        cols.append([c[r] for r in host_rows])
+                yield Frame(cols, schema.prefix)
+        return IterReader(gen())
+
+
 class Head(_PipelinedSlice):
     """First n rows per shard (slice.go:966-994)."""
 
@@ -408,6 +472,10 @@ def _coerce_columns(cols: List, schema: Schema, device: str) -> List:
     for c, dt in zip(cols, schema.dtypes):
         if is_object(dt):
             out.append(c if isinstance(c, list) else c.cpu().tolist())
+        elif isinstance(c, BytesColumn) and dt == BYTES:
+            if device != "cpu" and not c.data.is_cuda:
+                c = c.to(device, non_blocking=True)
+            out.append(c)
         else:
             if not isinstance(c, torch.Tensor):
                 c = torch.tensor(c, dtype=dt)

@@ -2,8 +2,9 @@
 
 fast_wordcount: the reference's headline wordcount
 (docs/index.md:93-155) restructured so the aggregation runs on the
-GPU: the rowwise tokenizer (unavoidably host-side in Python)
-dictionary-encodes words to 64-bit murmur hashes AND emits each
+GPU: the rowwise tokenizer (host-side Python in this recipe; see
+device_wordcount for the device tokenizer) dictionary-encodes words to
+64-bit murmur hashes AND emits each
 shard's (id -> word) mapping only once per new word, so the count
 Reduce runs device-native over int64 ids and only the small distinct
 mapping flows on the host path.
@@ -14,7 +15,13 @@ encoding (3.5 s vs 8.6 s) — Python tokenization dominates both and a
 C-level dict count beats the extra per-word hash pass.  The K17
 DEVICE-side variant flips this: gpu_wordcount (batch byte packing +
 device murmur ids + device count) measures 7.5 M words/s vs 5.2 M for
-the string-keyed path at 4M words (benchmarks/wc_ab.py).
+the string-keyed path at 4M words (benchmarks/wc_ab.py).  Both still
+tokenize in Python, and that is their time: device_wordcount, which
+splits on the device too (K20, csrc/tokenize.hip), measures 170 ms for
+the same 4M words (23.6 M words/s) against 558 ms for gpu_wordcount,
+616 ms for a BYTES column packed from host tokens and 667 ms for the
+string-keyed path, all four in one process
+(profiles/wordcount_ab_tokenize.txt).
 
 Collision note: ids are murmur3-64 (two murmur3-32 lanes); distinct
 words colliding would merge counts with probability ~V^2/2^65 —
@@ -84,6 +91,28 @@ def fast_wordcount(nshard: int, open_fn: Callable[[], Iterable[str]]
         return (words[0], sum(cs))
 
     return Map(joined, resolve, out_schema=(str, int), rowwise=True)
+
+
+# -- device_wordcount: tokenize, hash and count on device -----------------
+
+def device_wordcount(nshard: int, open_fn: Callable[[], Iterable[str]]
+                     ) -> Slice:
+    """Slice<word: bytes, count: int>: ScanReader -> Tokenize -> Map
+    (word, 1) -> Reduce("sum").  Lines pack into a BytesColumn per
+    batch; splitting (K20), hashing, partitioning and the string-keyed
+    count all run on the session device, with no per-word Python.
+    Words split on ASCII whitespace (bytes.split()).  Exact up to the
+    2^-64 dictionary-id collision BytesColumn documents.  Build inside
+    a bigslice_amd.func."""
+    import torch
+
+    from .ops import Tokenize
+    words = Tokenize(ScanReader(nshard, open_fn))
+    pairs = Map(words,
+                lambda w: (w, torch.ones(len(w), dtype=torch.int64,
+                                         device=w.device)),
+                out_schema=(bytes, int))
+    return Reduce(pairs, "sum")
 
 
 # -- gpu_wordcount: device dictionary ids via K17 ------------------------

@@ -3,6 +3,7 @@
   python -m bigslice_amd.tools.microprof groupby --rows 125000000
   python -m bigslice_amd.tools.microprof partition --rows 125000000
   python -m bigslice_amd.tools.microprof hash --rows 125000000
+  python -m bigslice_amd.tools.microprof tokenize --iters 20
 
 Times each kernel phase with hipEvents over --iters iterations.  Keep
 runs short: this is the target for `rocprofv3 --pmc ... -- ...`.
@@ -42,13 +43,51 @@ def timeit(fn, iters):
     return ts[len(ts) // 2]
 
 
+def tokenize_ab(dev, g, iters, nbytes=64 << 20):
+    """BytesColumn.split on one warm batch of synthetic text (8-byte
+    words, single spaces, 64-byte lines, one row per line): the K20
+    kernels against split_torch on the same device tensors, in this
+    process.  Wall time per call, readback of the totals included."""
+    from bigslice_amd.frame import BytesColumn, split_torch
+    nlines = nbytes // 64
+    text = torch.randint(97, 123, (nlines, 64), dtype=torch.uint8,
+                         device=dev, generator=g)
+    text[:, 8::9] = 32
+    text[:, 63] = 10
+    col = BytesColumn(
+        text.flatten(),
+        torch.arange(nlines + 1, dtype=torch.int64, device=dev) * 64)
+    mask4 = kernels.tokenize_mask(None)
+    out = {"which": "tokenize", "bytes": nbytes, "rows": nlines}
+    for with_rows in (False, True):
+        nat = kernels.tokenize_bytes(col.data, col.offsets, mask4,
+                                     with_rows)
+        ref = split_torch(col.data, col.offsets, mask4, with_rows)
+        assert all(torch.equal(a, b) for a, b in zip(nat, ref))
+        out["tokens"] = nat[1].shape[0] - 1
+        del nat, ref
+        tag = "_rows" if with_rows else ""
+        # the torch path first: it has the larger footprint, so the
+        # allocator is at its peak before either arm is timed
+        t_ms = timeit(lambda: split_torch(col.data, col.offsets, mask4,
+                                          with_rows), iters)
+        n_ms = timeit(lambda: kernels.tokenize_bytes(
+            col.data, col.offsets, mask4, with_rows), iters)
+        out["torch%s_ms" % tag] = t_ms
+        out["native%s_ms" % tag] = n_ms
+        out["torch%s_gbps" % tag] = nbytes / t_ms / 1e6
+        out["native%s_gbps" % tag] = nbytes / n_ms / 1e6
+    out["split_ms"] = timeit(lambda: col.split(), iters)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", choices=["groupby", "groupby_pp", "groupby_part",
                                       "insert", "insert_rep",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
-                                      "runs"])
+                                      "runs", "tokenize"])
     ap.add_argument("--nrep", type=int, default=8)
     ap.add_argument("--cap", type=int, default=0,
                     help="table capacity (0 = 2x nkeys rounded up)")
@@ -61,6 +100,9 @@ def main():
     dev = "cuda:0"
     g = torch.Generator(device=dev)
     g.manual_seed(1)
+    if args.which == "tokenize":
+        print(json.dumps(tokenize_ab(dev, g, args.iters)))
+        return
     keys = torch.randint(0, args.nkeys, (args.rows,), dtype=torch.int64,
                          device=dev, generator=g)
     vals = torch.ones(args.rows, dtype=torch.int64, device=dev)
