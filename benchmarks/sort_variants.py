@@ -1,4 +1,10 @@
-"""In-process A/B of hand radix-sort geometry variants vs rocPRIM.
+"""In-process A/B of the two hand radix-sort shapes vs rocPRIM.
+
+  python benchmarks/sort_variants.py [rows] [shapes]
+
+shapes: comma-separated BIGSLICE_RADIX_VARIANT values, 0 (the default
+shape: split reorder, 512 threads) and/or 2 (monolithic, 1024 threads).
+The "auto" arm is the production dispatch on the default shape.
 
 All arms run in ONE process on ONE box back-to-back, so DVFS/box
 variance cancels (guide §5.4: never compare across runs)."""
@@ -51,20 +57,28 @@ def main():
         srt = torch.sort(k, stable=True)
         ref[name] = (srt.values, srt.indices.to(torch.int64))
 
+    # every arm states all three switches; None = unset
     arms = [("auto", {"BIGSLICE_SORT_ROCPRIM": "0",
                       "BIGSLICE_SORT_HAND": "0",
-                      "BIGSLICE_RADIX_VARIANT": "2"}),
+                      "BIGSLICE_RADIX_VARIANT": None}),
             ("rocprim", {"BIGSLICE_SORT_ROCPRIM": "1",
-                         "BIGSLICE_SORT_HAND": "0"})]
-    vars_arg = sys.argv[2] if len(sys.argv) > 2 else "2"
+                         "BIGSLICE_SORT_HAND": "0",
+                         "BIGSLICE_RADIX_VARIANT": None})]
+    vars_arg = sys.argv[2] if len(sys.argv) > 2 else "0,2"
     for var in (int(x) for x in vars_arg.split(",")):
+        if var not in (0, 2):
+            sys.exit(f"shape {var}: only 0 and 2 exist")
         arms.append((f"hand v{var}",
                      {"BIGSLICE_SORT_ROCPRIM": "0",
                       "BIGSLICE_SORT_HAND": "1",
                       "BIGSLICE_RADIX_VARIANT": str(var)}))
     for rounds in range(2):  # two rounds to expose drift
         for name, env in arms:
-            os.environ.update(env)
+            for key, val in env.items():
+                if val is None:
+                    os.environ.pop(key, None)
+                else:
+                    os.environ[key] = val
             line = f"[r{rounds}] {name:10s}"
             for dist, (k, v) in data.items():
                 ms = timeit(lambda: _C.radix_sort_kv(k, v))

@@ -219,9 +219,45 @@ ValCols make_val_cols(const std::vector<torch::Tensor>& vals,
   return vc;
 }
 
-// Streaming insert into a caller-owned table (tkeys: cap+1 slots filled
-// with the sentinel; tabs[c]: cap+1 slots at the agg identity; flags:
-// int32[2] = {sentinel_seen, overflow}).  Multiple insert calls
+// Hash seed of every combiner table (the reference combiner's
+// hashSeed): not the partitioner's, so a previous partitioning step
+// does not strip hash entropy.
+constexpr uint32_t GB_HASH_SEED = 0x9acb0442u;
+
+// A caller-owned table: tkeys holds cap+1 slots filled with the
+// sentinel (cap a power of two; slot cap takes the sentinel key itself),
+// every tab cap+1 slots at its agg identity, flags is int32[2] =
+// {sentinel_seen, overflow}.  Returns cap.
+int64_t table_cap(const torch::Tensor& tkeys,
+                  at::ArrayRef<torch::Tensor> tabs,
+                  const torch::Tensor& flags) {
+  const int64_t cap = tkeys.size(0) - 1;
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0, "capacity must be 2^k");
+  TORCH_CHECK(tkeys.is_cuda() && tkeys.is_contiguous() &&
+              tkeys.scalar_type() == torch::kInt64);
+  for (const auto& tab : tabs)
+    TORCH_CHECK(tab.is_cuda() && tab.is_contiguous() &&
+                tab.size(0) == cap + 1);
+  TORCH_CHECK(flags.is_cuda() && flags.is_contiguous() &&
+              flags.scalar_type() == torch::kInt32 && flags.numel() >= 2);
+  return cap;
+}
+
+// Bucket id of the partitioned insert = slot >> shift: the high bits of
+// the table slot, for nbuckets buckets over cap slots.
+uint32_t bucket_shift(int64_t cap, int64_t nbuckets) {
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && cap <= (int64_t(1) << 31),
+              "capacity must be 2^k");
+  TORCH_CHECK(nbuckets >= 2 && nbuckets <= GBP_MAX_BUCKETS &&
+                  (nbuckets & (nbuckets - 1)) == 0 && nbuckets <= cap,
+              "nbuckets must be a power of two in [2, ", GBP_MAX_BUCKETS,
+              "] and at most the capacity");
+  uint32_t shift = 0;
+  while ((cap >> shift) > nbuckets) ++shift;
+  return shift;
+}
+
+// Streaming insert into a caller-owned table.  Multiple insert calls
 // accumulate into the same table; the host checks flags[1] after
 // compaction and regrows on overflow.
 void groupby_insert(torch::Tensor keys, std::vector<torch::Tensor> vals,
@@ -232,14 +268,12 @@ void groupby_insert(torch::Tensor keys, std::vector<torch::Tensor> vals,
   keys = keys.contiguous();
   int64_t n = keys.size(0);
   if (n == 0) return;
-  int64_t cap = tkeys.size(0) - 1;
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0, "capacity must be 2^k");
+  int64_t cap = table_cap(tkeys, tabs, flags);
   ValCols vc = make_val_cols(vals, tabs, aggs);
-  const uint32_t seed = 0x9acb0442u;  // reference combiner hashSeed
   int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
   hipLaunchKernelGGL(k_groupby_insert, dim3(blocks), dim3(THREADS), 0,
                      current_stream(), keys.data_ptr<int64_t>(), n, vc,
-                     tkeys.data_ptr<int64_t>(), cap, seed,
+                     tkeys.data_ptr<int64_t>(), cap, GB_HASH_SEED,
                      flags.data_ptr<int32_t>(),
                      flags.data_ptr<int32_t>() + 1, max_probes);
   HIP_CHECK(hipGetLastError());
@@ -254,27 +288,26 @@ torch::Tensor slot_pids(torch::Tensor keys, int64_t cap,
   int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
   hipLaunchKernelGGL(k_slot_pids, dim3(blocks), dim3(THREADS), 0,
                      current_stream(), keys.data_ptr<int64_t>(), n, cap,
-                     (int32_t)nparts, 0x9acb0442u,
+                     (int32_t)nparts, GB_HASH_SEED,
                      pids.data_ptr<int32_t>());
   HIP_CHECK(hipGetLastError());
   return pids;
 }
 
-// Two-level LDS insert (single int64 SUM value): see groupby.hip.
+// Two-level LDS insert (single int64 SUM value): see groupby.hip.  The
+// kernel's sample-adaptive and global-only settings have no caller
+// left: it always runs with its LDS tier on and no hit counter.
 void groupby_insert_lds(torch::Tensor keys, torch::Tensor vals,
                         torch::Tensor tkeys, torch::Tensor tab,
                         torch::Tensor flags, int64_t max_probes,
-                        int64_t force, int64_t target_blocks,
-                        torch::Tensor hits) {
+                        int64_t target_blocks) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   TORCH_CHECK(vals.scalar_type() == torch::kInt64);
   keys = keys.contiguous();
   vals = vals.contiguous();
   int64_t n = keys.size(0);
   if (n == 0) return;
-  int64_t cap = tkeys.size(0) - 1;
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0);
-  const uint32_t seed = 0x9acb0442u;
+  int64_t cap = table_cap(tkeys, {tab}, flags);
   // grid-stride geometry (matches the one-level kernel); target_blocks
   // caps the grid so the LDS flush volume stays bounded
   if (target_blocks <= 0) target_blocks = 32768;
@@ -285,11 +318,10 @@ void groupby_insert_lds(torch::Tensor keys, torch::Tensor vals,
                      dim3(THREADS), 0, current_stream(),
                      keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
                      tkeys.data_ptr<int64_t>(),
-                     (long long*)tab.data_ptr<int64_t>(), cap, seed,
+                     (long long*)tab.data_ptr<int64_t>(), cap, GB_HASH_SEED,
                      flags.data_ptr<int32_t>(),
                      flags.data_ptr<int32_t>() + 1, max_probes, rpb,
-                     (int32_t)force,
-                     hits.numel() ? (uint32_t*)hits.data_ptr() : nullptr);
+                     /*force=*/(int32_t)1, /*global_hits=*/(uint32_t*)nullptr);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -301,16 +333,9 @@ std::tuple<torch::Tensor, torch::Tensor> part_scatter_impl(
     int64_t nbuckets) {
   int64_t n = keys.size(0);
   TORCH_CHECK(n > 0 && n < (int64_t(1) << 31), "1 <= rows < 2^31");
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && cap <= (int64_t(1) << 31),
-              "capacity must be 2^k");
-  TORCH_CHECK(nbuckets >= 2 && nbuckets <= GBP_MAX_BUCKETS &&
-                  (nbuckets & (nbuckets - 1)) == 0 && nbuckets <= cap,
-              "nbuckets must be a power of two in [2, ", GBP_MAX_BUCKETS,
-              "] and at most the capacity");
-  const uint32_t seed = 0x9acb0442u;
+  const uint32_t shift = bucket_shift(cap, nbuckets);
+  const uint32_t seed = GB_HASH_SEED;
   const uint32_t mask = (uint32_t)(cap - 1);
-  uint32_t shift = 0;
-  while ((cap >> shift) > nbuckets) ++shift;
   const uint32_t nb = (uint32_t)nbuckets;
   const int64_t ntiles = (n + GBP_SCATTER_ROWS - 1) / GBP_SCATTER_ROWS;
   auto opts32 = keys.options().dtype(torch::kInt32);
@@ -339,6 +364,24 @@ std::tuple<torch::Tensor, torch::Tensor> part_scatter_impl(
   return {pairs, totals};
 }
 
+// Tiled aggregate with its global flush over already partitioned pairs.
+void launch_gbp_aggregate(const torch::Tensor& pairs,
+                          const torch::Tensor& tkeys,
+                          const torch::Tensor& tab,
+                          const torch::Tensor& flags, int64_t cap,
+                          int64_t max_probes) {
+  const int64_t n = pairs.size(0);
+  const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
+  hipLaunchKernelGGL(k_gbp_aggregate, dim3((uint32_t)ntiles),
+                     dim3(GBP_THREADS), 0, current_stream(),
+                     (const GbPair*)pairs.data_ptr<int64_t>(), n,
+                     tkeys.data_ptr<int64_t>(),
+                     (long long*)tab.data_ptr<int64_t>(), cap, GB_HASH_SEED,
+                     flags.data_ptr<int32_t>(),
+                     flags.data_ptr<int32_t>() + 1, max_probes);
+  HIP_CHECK(hipGetLastError());
+}
+
 // Owner pass + cleanup pass over already partitioned pairs (see "Owned
 // slices" in groupby_part.hip).  pairs is reordered in place (spilled
 // rows move to the front of the region their owner consumed).  Returns
@@ -350,27 +393,18 @@ torch::Tensor part_owned_impl(const torch::Tensor& pairs,
                               const torch::Tensor& flags,
                               int64_t max_probes) {
   const int64_t n = pairs.size(0);
-  const int64_t cap = tkeys.size(0) - 1;
+  const int64_t cap = table_cap(tkeys, {tab}, flags);
   const int64_t nbuckets = totals.size(0);
   TORCH_CHECK(n > 0 && n < (int64_t(1) << 31), "1 <= rows < 2^31");
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && cap <= (int64_t(1) << 31),
-              "capacity must be 2^k");
-  TORCH_CHECK(nbuckets >= 2 && nbuckets <= GBP_MAX_BUCKETS &&
-                  (nbuckets & (nbuckets - 1)) == 0 && nbuckets <= cap,
-              "nbuckets must be a power of two in [2, ", GBP_MAX_BUCKETS,
-              "] and at most the capacity");
+  const uint32_t shift = bucket_shift(cap, nbuckets);
   const int64_t S = cap / nbuckets;
   TORCH_CHECK(S <= GBP_LDS_SLOTS, "owned pass needs capacity / nbuckets <= ",
               GBP_LDS_SLOTS);
-  TORCH_CHECK(tab.size(0) == cap + 1 && tkeys.is_contiguous() &&
-              tab.is_contiguous());
   TORCH_CHECK((uintptr_t)tkeys.data_ptr() % 16 == 0 &&
                   (uintptr_t)tab.data_ptr() % 16 == 0,
               "table must be 16-byte aligned");
-  uint32_t shift = 0;
-  while ((cap >> shift) > nbuckets) ++shift;
   const uint32_t nb = (uint32_t)nbuckets;
-  const uint32_t seed = 0x9acb0442u;
+  const uint32_t seed = GB_HASH_SEED;
   auto clean = torch::empty({nbuckets}, totals.options());
   auto todo = torch::empty({nbuckets, 2}, totals.options());
   auto stream = current_stream();
@@ -414,26 +448,15 @@ void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
   TORCH_CHECK(tab.scalar_type() == torch::kInt64);
   keys = keys.contiguous();
   vals = vals.contiguous();
-  int64_t n = keys.size(0);
-  if (n == 0) return;
-  int64_t cap = tkeys.size(0) - 1;
+  if (keys.size(0) == 0) return;
+  int64_t cap = table_cap(tkeys, {tab}, flags);
   auto parts = part_scatter_impl(keys, vals, cap, nbuckets);
   const torch::Tensor& pairs = std::get<0>(parts);
-  if (owned) {
+  if (owned)
     part_owned_impl(pairs, std::get<1>(parts), tkeys, tab, flags,
                     max_probes);
-    return;
-  }
-  const uint32_t seed = 0x9acb0442u;
-  const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
-  hipLaunchKernelGGL(k_gbp_aggregate, dim3((uint32_t)ntiles),
-                     dim3(GBP_THREADS), 0, current_stream(),
-                     (const GbPair*)pairs.data_ptr<int64_t>(), n,
-                     tkeys.data_ptr<int64_t>(),
-                     (long long*)tab.data_ptr<int64_t>(), cap, seed,
-                     flags.data_ptr<int32_t>(),
-                     flags.data_ptr<int32_t>() + 1, max_probes);
-  HIP_CHECK(hipGetLastError());
+  else
+    launch_gbp_aggregate(pairs, tkeys, tab, flags, cap, max_probes);
 }
 
 // The scatter alone (tests, kernel timing): (pairs [n, 2], rows per
@@ -455,19 +478,10 @@ void groupby_part_aggregate(torch::Tensor pairs, torch::Tensor tkeys,
   TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt64 &&
               pairs.is_contiguous() && pairs.dim() == 2 &&
               pairs.size(1) == 2);
-  int64_t n = pairs.size(0);
-  if (n == 0) return;
-  int64_t cap = tkeys.size(0) - 1;
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0);
-  const int64_t ntiles = (n + GBP_TILE_ROWS - 1) / GBP_TILE_ROWS;
-  hipLaunchKernelGGL(k_gbp_aggregate, dim3((uint32_t)ntiles),
-                     dim3(GBP_THREADS), 0, current_stream(),
-                     (const GbPair*)pairs.data_ptr<int64_t>(), n,
-                     tkeys.data_ptr<int64_t>(),
-                     (long long*)tab.data_ptr<int64_t>(), cap, 0x9acb0442u,
-                     flags.data_ptr<int32_t>(),
-                     flags.data_ptr<int32_t>() + 1, max_probes);
-  HIP_CHECK(hipGetLastError());
+  if (pairs.size(0) == 0) return;
+  TORCH_CHECK(tab.scalar_type() == torch::kInt64);
+  launch_gbp_aggregate(pairs, tkeys, tab, flags,
+                       table_cap(tkeys, {tab}, flags), max_probes);
 }
 
 // Owner + cleanup passes alone over already partitioned pairs and their
@@ -483,106 +497,6 @@ torch::Tensor groupby_part_owned(torch::Tensor pairs, torch::Tensor totals,
               totals.is_contiguous() && totals.dim() == 1);
   TORCH_CHECK(tab.scalar_type() == torch::kInt64);
   return part_owned_impl(pairs, totals, tkeys, tab, flags, max_probes);
-}
-
-// Multi-row software-pipelined one-level insert (single int64 SUM
-// value): see groupby.hip.
-void groupby_insert_mlp(torch::Tensor keys, torch::Tensor vals,
-                        torch::Tensor tkeys, torch::Tensor tab,
-                        torch::Tensor flags, int64_t max_probes) {
-  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
-  TORCH_CHECK(vals.scalar_type() == torch::kInt64);
-  keys = keys.contiguous();
-  vals = vals.contiguous();
-  int64_t n = keys.size(0);
-  if (n == 0) return;
-  int64_t cap = tkeys.size(0) - 1;
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0);
-  const uint32_t seed = 0x9acb0442u;
-  int64_t nblocks = std::min<int64_t>(
-      (n + THREADS * 4 - 1) / (THREADS * 4), 32768);
-  hipLaunchKernelGGL(k_groupby_insert_sum_i64_mlp, dim3((uint32_t)nblocks),
-                     dim3(THREADS), 0, current_stream(),
-                     keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
-                     tkeys.data_ptr<int64_t>(),
-                     (long long*)tab.data_ptr<int64_t>(), cap, seed,
-                     flags.data_ptr<int32_t>(),
-                     flags.data_ptr<int32_t>() + 1, max_probes);
-  HIP_CHECK(hipGetLastError());
-}
-
-// Packed-slot fast path (single int64 SUM value): see groupby.hip.
-void groupby_insert_packed(torch::Tensor keys, torch::Tensor vals,
-                           torch::Tensor table, torch::Tensor flags,
-                           int64_t max_probes) {
-  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
-  TORCH_CHECK(vals.scalar_type() == torch::kInt64);
-  keys = keys.contiguous();
-  vals = vals.contiguous();
-  int64_t n = keys.size(0);
-  if (n == 0) return;
-  int64_t cap = table.size(0) / 2 - 1;
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0);
-  const uint32_t seed = 0x9acb0442u;
-  int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
-  hipLaunchKernelGGL(k_groupby_insert_packed_sum_i64, dim3(blocks),
-                     dim3(THREADS), 0, current_stream(),
-                     keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
-                     table.data_ptr<int64_t>(), cap, seed,
-                     flags.data_ptr<int32_t>(),
-                     flags.data_ptr<int32_t>() + 1, max_probes);
-  HIP_CHECK(hipGetLastError());
-}
-
-// Replicated-insert experiment (see k_groupby_insert_packed_rep):
-// `table` holds nrep packed tables back to back.
-void groupby_insert_packed_rep(torch::Tensor keys, torch::Tensor vals,
-                               torch::Tensor table, int64_t nrep,
-                               torch::Tensor flags, int64_t max_probes) {
-  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
-  keys = keys.contiguous();
-  vals = vals.contiguous();
-  int64_t n = keys.size(0);
-  if (n == 0) return;
-  int64_t cap = table.size(0) / (2 * nrep) - 1;
-  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0);
-  const uint32_t seed = 0x9acb0442u;
-  int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
-  hipLaunchKernelGGL(k_groupby_insert_packed_rep, dim3(blocks),
-                     dim3(THREADS), 0, current_stream(),
-                     keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
-                     table.data_ptr<int64_t>(), cap, (int32_t)nrep, seed,
-                     flags.data_ptr<int32_t>(),
-                     flags.data_ptr<int32_t>() + 1, max_probes);
-  HIP_CHECK(hipGetLastError());
-}
-
-std::vector<torch::Tensor> groupby_compact_packed(torch::Tensor table,
-                                                  torch::Tensor cursor) {
-  int64_t cap = table.size(0) / 2 - 1;
-  auto out_keys = torch::empty({cap}, table.options());
-  auto out_vals = torch::empty({cap}, table.options());
-  int64_t spb = (cap + 2047) / 2048;
-  if (spb < THREADS) spb = THREADS;
-  int blocks = (int)((cap + spb - 1) / spb);
-  hipLaunchKernelGGL(k_groupby_compact_packed, dim3(blocks), dim3(THREADS),
-                     0, current_stream(), table.data_ptr<int64_t>(), cap,
-                     spb, out_keys.data_ptr<int64_t>(),
-                     out_vals.data_ptr<int64_t>(),
-                     (unsigned long long*)cursor.data_ptr());
-  HIP_CHECK(hipGetLastError());
-  return {out_keys, out_vals};
-}
-
-torch::Tensor alloc_packed_table(int64_t cap, torch::Tensor like) {
-  auto table = torch::empty({2 * (cap + 1)}, like.options());
-  int64_t nslots = cap + 1;
-  int blocks = (int)std::min<int64_t>((nslots + THREADS - 1) / THREADS,
-                                      16384);
-  hipLaunchKernelGGL(k_fill_packed_slots, dim3(blocks), dim3(THREADS), 0,
-                     current_stream(), table.data_ptr<int64_t>(), nslots);
-  HIP_CHECK(hipGetLastError());
-  return table;
 }
 
 // Compact used slots into freshly-allocated output arrays; returns
@@ -629,15 +543,15 @@ static bool force_rocprim_sort() {
   return e && e[0] == '1';
 }
 
-// Geometry A/B harness: BIGSLICE_RADIX_VARIANT selects (tile, block).
-// Re-read each call so one process can A/B variants back-to-back.
+// Geometry A/B harness: BIGSLICE_RADIX_VARIANT=2 selects the monolithic
+// shape (see hand_radix_sort).  Re-read each call so one process can A/B
+// the shapes back-to-back.
 static int radix_variant() {
   const char* e = getenv("BIGSLICE_RADIX_VARIANT");
   return e ? atoi(e) : 0;
 }
 
-template <typename K, int HAS_VAL, int TILE, int BLOCK, int SPLIT,
-          int PERSIST = 0, int NT = 0, int CHUNKED = 0, int WPS = 8>
+template <typename K, int HAS_VAL, int TILE, int BLOCK, int SPLIT>
 static void hand_radix_passes(const torch::Tensor& keys,
                               const torch::Tensor& vals,
                               torch::Tensor& keys_out,
@@ -692,33 +606,13 @@ static void hand_radix_passes(const torch::Tensor& keys,
                                RDX_RADIX * 8, stream));
     HIP_CHECK(hipMemsetAsync(state.data_ptr(), 0,
                              (size_t)ntiles * RDX_RADIX * 8, stream));
-    if (CHUNKED) {
-      hipLaunchKernelGGL(
-          (k_radix_scatter_chunked<K, HAS_VAL, TILE, BLOCK, WPS>),
-          dim3((int)ntiles), dim3(BLOCK), 0, stream, src_k, dst_k,
-          src_v, dst_v, n, passes[i] * 8, bias,
-          (const unsigned long long*)dbase.data_ptr<int64_t>(),
-          (unsigned long long*)state.data_ptr<int64_t>(), next_shift,
-          (unsigned long long*)hist_next.data_ptr<int64_t>());
-    } else if (PERSIST) {
-      const int grid = (int)std::min<int64_t>(ntiles, 256);
-      hipLaunchKernelGGL(
-          (k_radix_scatter_persist<K, HAS_VAL, TILE, BLOCK>),
-          dim3(grid), dim3(BLOCK), 0, stream, src_k, dst_k, src_v,
-          dst_v, n, passes[i] * 8, bias,
-          (const unsigned long long*)dbase.data_ptr<int64_t>(),
-          (unsigned long long*)state.data_ptr<int64_t>(), next_shift,
-          (unsigned long long*)hist_next.data_ptr<int64_t>());
-    } else {
-      hipLaunchKernelGGL(
-          (k_radix_scatter<K, HAS_VAL, TILE, BLOCK, SPLIT, NT>),
-          dim3((int)ntiles),
-          dim3(BLOCK), 0, stream, src_k, dst_k, src_v, dst_v, n,
-          passes[i] * 8, bias,
-          (const unsigned long long*)dbase.data_ptr<int64_t>(),
-          (unsigned long long*)state.data_ptr<int64_t>(), next_shift,
-          (unsigned long long*)hist_next.data_ptr<int64_t>());
-    }
+    hipLaunchKernelGGL(
+        (k_radix_scatter<K, HAS_VAL, TILE, BLOCK, SPLIT>),
+        dim3((int)ntiles), dim3(BLOCK), 0, stream, src_k, dst_k, src_v,
+        dst_v, n, passes[i] * 8, bias,
+        (const unsigned long long*)dbase.data_ptr<int64_t>(),
+        (unsigned long long*)state.data_ptr<int64_t>(), next_shift,
+        (unsigned long long*)hist_next.data_ptr<int64_t>());
     HIP_CHECK(hipGetLastError());
     src_k = dst_k;
     src_v = dst_v;
@@ -769,48 +663,15 @@ static void hand_radix_sort(const torch::Tensor& keys,
   const int width = (int)keys.element_size() * 8;
   const int npass = width / 8;
   const uint64_t bias = 1ull << (width - 1);
-  switch (radix_variant()) {
-    case 1:
-      hand_radix_passes<K, HAS_VAL, 4096, 512, 0>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 2:
-      hand_radix_passes<K, HAS_VAL, 8192, 1024, 0>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 5:
-      hand_radix_passes<K, HAS_VAL, 4096, 512, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 6:
-      hand_radix_passes<K, HAS_VAL, 3584, 512, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 8:
-      hand_radix_passes<K, HAS_VAL, 8192, 1024, 0, 0, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 7:
-      hand_radix_passes<K, HAS_VAL, 8192, 1024, 0, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 9:
-      // chunked reorder (rocPRIM-occupancy experiment, measured
-      // SLOWER: see k_radix_scatter_chunked's header comment)
-      hand_radix_passes<K, HAS_VAL, 4096, 512, 0, 0, 0, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 10:
-      hand_radix_passes<K, HAS_VAL, 8192, 1024, 0, 0, 0, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-      break;
-    case 0:
-    case 3:
-    default:
-      // default: split reorder, 8K tiles, two workgroups per CU
-      hand_radix_passes<K, HAS_VAL, 8192, 512, 1>(
-          keys, vals, keys_out, vals_out, passes, npass, bias, stream);
-  }
+  if (radix_variant() == 2)
+    // monolithic: 8K tiles, both columns staged, one 1024-thread
+    // workgroup per CU (the shape of profiles/sort_variants*.txt)
+    hand_radix_passes<K, HAS_VAL, 8192, 1024, 0>(
+        keys, vals, keys_out, vals_out, passes, npass, bias, stream);
+  else
+    // default: split reorder, 8K tiles, two workgroups per CU
+    hand_radix_passes<K, HAS_VAL, 8192, 512, 1>(
+        keys, vals, keys_out, vals_out, passes, npass, bias, stream);
 }
 
 // Production dispatch: the AND/OR probe picks the executed byte set.
@@ -837,41 +698,64 @@ static bool use_hand_path(const std::vector<int>& passes) {
   return !contiguous;
 }
 
+// The probe and the engine choice, for all three sorts.  Returns true
+// when the result is already in keys_out (and vals_out): every byte was
+// constant and the input went through as it is, or the hand path ran.
+// Otherwise narrows [begin_bit, end_bit) for rocPRIM.
+template <int HAS_VAL>
+static bool sort_probed(const torch::Tensor& keys, const torch::Tensor& vals,
+                        torch::Tensor& keys_out, torch::Tensor& vals_out,
+                        int& begin_bit, int& end_bit) {
+  if (keys.size(0) == 0 || !probed_sortable(keys)) return false;
+  const bool i64 = keys.scalar_type() == torch::kInt64;
+  std::vector<int> passes =
+      i64 ? probe_passes<int64_t>(keys) : probe_passes<int32_t>(keys);
+  if (passes.empty()) {
+    keys_out.copy_(keys);
+    if (HAS_VAL) vals_out.copy_(vals);
+    return true;
+  }
+  if (use_hand_path(passes)) {
+    if (i64)
+      hand_radix_sort<int64_t, HAS_VAL>(keys, vals, keys_out, vals_out,
+                                        passes);
+    else
+      hand_radix_sort<int32_t, HAS_VAL>(keys, vals, keys_out, vals_out,
+                                        passes);
+    return true;
+  }
+  begin_bit = passes.front() * 8;
+  end_bit = (passes.back() + 1) * 8;
+  return false;
+}
+
+// rocPRIM's two-call protocol: call(nullptr, bytes) reports the
+// temporary storage it needs, the second call runs in it.
+template <typename F>
+static void with_rocprim_temp(const torch::Tensor& like, F call) {
+  size_t temp_bytes = 0;
+  call((void*)nullptr, temp_bytes);
+  auto temp = torch::empty({(int64_t)temp_bytes},
+                           like.options().dtype(torch::kUInt8));
+  call(temp.data_ptr(), temp_bytes);
+}
+
 torch::Tensor radix_sort_keys(torch::Tensor keys, bool probe) {
   TORCH_CHECK(keys.is_cuda() && keys.is_contiguous());
   int64_t n = keys.size(0);
   auto keys_out = torch::empty_like(keys);
   int begin_bit = 0, end_bit = (int)keys.element_size() * 8;
+  torch::Tensor nil;
   // probe=false: full-width rocPRIM with no byte-constancy probe (the
   // probe's host readback is a stream sync — callers that must stay
   // async, like the cardinality sample, opt out)
-  if (probe && n > 0 && probed_sortable(keys)) {
-    std::vector<int> passes =
-        keys.scalar_type() == torch::kInt64
-            ? probe_passes<int64_t>(keys) : probe_passes<int32_t>(keys);
-    if (passes.empty()) {
-      keys_out.copy_(keys);
-      return keys_out;
-    }
-    if (use_hand_path(passes)) {
-      torch::Tensor nil;
-      if (keys.scalar_type() == torch::kInt64)
-        hand_radix_sort<int64_t, 0>(keys, nil, keys_out, nil, passes);
-      else
-        hand_radix_sort<int32_t, 0>(keys, nil, keys_out, nil, passes);
-      return keys_out;
-    }
-    begin_bit = passes.front() * 8;
-    end_bit = (passes.back() + 1) * 8;
-  }
+  if (probe && sort_probed<0>(keys, nil, keys_out, nil, begin_bit, end_bit))
+    return keys_out;
   auto run = [&](auto fn) {
-    size_t temp_bytes = 0;
-    fn(keys.data_ptr(), keys_out.data_ptr(), n, begin_bit, end_bit,
-       nullptr, temp_bytes, current_stream());
-    auto temp = torch::empty({(int64_t)temp_bytes},
-                             keys.options().dtype(torch::kUInt8));
-    fn(keys.data_ptr(), keys_out.data_ptr(), n, begin_bit, end_bit,
-       temp.data_ptr(), temp_bytes, current_stream());
+    with_rocprim_temp(keys, [&](void* temp, size_t& temp_bytes) {
+      fn(keys.data_ptr(), keys_out.data_ptr(), n, begin_bit, end_bit, temp,
+         temp_bytes, current_stream());
+    });
   };
   switch (keys.scalar_type()) {
     case torch::kInt64: run(radix_sort_keys_int64_t); break;
@@ -884,50 +768,23 @@ torch::Tensor radix_sort_keys(torch::Tensor keys, bool probe) {
   return keys_out;
 }
 
-// Direct (key, value) sort for 2-column frames: no permutation, no
-// gather passes.  The value column is bit-cast to int64 (it does not
-// participate in ordering).
-std::vector<torch::Tensor> radix_sort_kv(torch::Tensor keys,
-                                         torch::Tensor vals) {
-  TORCH_CHECK(keys.is_cuda() && keys.is_contiguous());
-  TORCH_CHECK(vals.is_cuda() && vals.is_contiguous());
-  TORCH_CHECK(vals.element_size() == 8, "8-byte values only");
+// Stable sort of (key, 8-byte value) pairs into fresh tensors; the
+// value column does not participate in ordering.
+static std::vector<torch::Tensor> sort_pairs(const torch::Tensor& keys,
+                                             const torch::Tensor& vals,
+                                             const char* unsupported) {
   int64_t n = keys.size(0);
   auto keys_out = torch::empty_like(keys);
   auto vals_out = torch::empty_like(vals);
   int begin_bit = 0, end_bit = (int)keys.element_size() * 8;
-  if (n > 0 && probed_sortable(keys)) {
-    std::vector<int> passes =
-        keys.scalar_type() == torch::kInt64
-            ? probe_passes<int64_t>(keys) : probe_passes<int32_t>(keys);
-    if (passes.empty()) {
-      keys_out.copy_(keys);
-      vals_out.copy_(vals);
-      return {keys_out, vals_out};
-    }
-    if (use_hand_path(passes)) {
-      if (keys.scalar_type() == torch::kInt64)
-        hand_radix_sort<int64_t, 1>(keys, vals, keys_out, vals_out,
-                                    passes);
-      else
-        hand_radix_sort<int32_t, 1>(keys, vals, keys_out, vals_out,
-                                    passes);
-      return {keys_out, vals_out};
-    }
-    begin_bit = passes.front() * 8;
-    end_bit = (passes.back() + 1) * 8;
-  }
+  if (sort_probed<1>(keys, vals, keys_out, vals_out, begin_bit, end_bit))
+    return {keys_out, vals_out};
   auto run = [&](auto fn) {
-    size_t temp_bytes = 0;
-    fn(keys.data_ptr(), keys_out.data_ptr(),
-       (const int64_t*)vals.data_ptr(), (int64_t*)vals_out.data_ptr(), n,
-       begin_bit, end_bit, nullptr, temp_bytes, current_stream());
-    auto temp = torch::empty({(int64_t)temp_bytes},
-                             keys.options().dtype(torch::kUInt8));
-    fn(keys.data_ptr(), keys_out.data_ptr(),
-       (const int64_t*)vals.data_ptr(), (int64_t*)vals_out.data_ptr(), n,
-       begin_bit, end_bit, temp.data_ptr(), temp_bytes,
-       current_stream());
+    with_rocprim_temp(keys, [&](void* temp, size_t& temp_bytes) {
+      fn(keys.data_ptr(), keys_out.data_ptr(),
+         (const int64_t*)vals.data_ptr(), (int64_t*)vals_out.data_ptr(), n,
+         begin_bit, end_bit, temp, temp_bytes, current_stream());
+    });
   };
   switch (keys.scalar_type()) {
     case torch::kInt64: run(radix_sort_pairs_int64_t); break;
@@ -935,9 +792,27 @@ std::vector<torch::Tensor> radix_sort_kv(torch::Tensor keys,
     case torch::kFloat32: run(radix_sort_pairs_float); break;
     case torch::kFloat64: run(radix_sort_pairs_double); break;
     default:
-      TORCH_CHECK(false, "radix_sort_kv: unsupported key dtype");
+      TORCH_CHECK(false, unsupported);
   }
   return {keys_out, vals_out};
+}
+
+// Direct (key, value) sort for 2-column frames: no permutation, no
+// gather passes.  The value column is bit-cast to int64.
+std::vector<torch::Tensor> radix_sort_kv(torch::Tensor keys,
+                                         torch::Tensor vals) {
+  TORCH_CHECK(keys.is_cuda() && keys.is_contiguous());
+  TORCH_CHECK(vals.is_cuda() && vals.is_contiguous());
+  TORCH_CHECK(vals.element_size() == 8, "8-byte values only");
+  return sort_pairs(keys, vals, "radix_sort_kv: unsupported key dtype");
+}
+
+// The sorting permutation: the row ids, sorted as the value column.
+torch::Tensor radix_argsort(torch::Tensor keys) {
+  TORCH_CHECK(keys.is_cuda() && keys.is_contiguous());
+  auto perm_in = torch::arange(keys.size(0),
+                               keys.options().dtype(torch::kInt64));
+  return sort_pairs(keys, perm_in, "radix_argsort: unsupported dtype")[1];
 }
 
 // K16: (unique_keys, aggregates, count) over key-sorted pairs via
@@ -958,17 +833,12 @@ std::vector<torch::Tensor> segment_reduce_sorted(torch::Tensor keys,
   auto count = torch::zeros({1}, keys.options());
   if (n == 0) return {uniq, aggs, count};
   auto run = [&](auto fn) {
-    size_t temp_bytes = 0;
-    fn(keys.data_ptr<int64_t>(), vals.data_ptr(), n,
-       uniq.data_ptr<int64_t>(), aggs.data_ptr(),
-       count.data_ptr<int64_t>(), (int)code, nullptr, temp_bytes,
-       current_stream());
-    auto temp = torch::empty({(int64_t)temp_bytes},
-                             keys.options().dtype(torch::kUInt8));
-    fn(keys.data_ptr<int64_t>(), vals.data_ptr(), n,
-       uniq.data_ptr<int64_t>(), aggs.data_ptr(),
-       count.data_ptr<int64_t>(), (int)code, temp.data_ptr(), temp_bytes,
-       current_stream());
+    with_rocprim_temp(keys, [&](void* temp, size_t& temp_bytes) {
+      fn(keys.data_ptr<int64_t>(), vals.data_ptr(), n,
+         uniq.data_ptr<int64_t>(), aggs.data_ptr(),
+         count.data_ptr<int64_t>(), (int)code, temp, temp_bytes,
+         current_stream());
+    });
   };
   switch (vals.scalar_type()) {
     case torch::kInt64: run(reduce_by_key_int64_t); break;
@@ -1044,17 +914,12 @@ std::vector<torch::Tensor> runs_sorted(torch::Tensor keys) {
   if (n == 0) return {uniq, starts, count};
   const char* rp = getenv("BIGSLICE_RUNS_ROCPRIM");
   if (rp && rp[0] == '1') {
-    size_t temp_bytes = 0;
-    runs_sorted_i64(keys.data_ptr<int64_t>(), n,
-                    uniq.data_ptr<int64_t>(), starts.data_ptr<int64_t>(),
-                    count.data_ptr<int64_t>(), nullptr, temp_bytes,
-                    current_stream());
-    auto temp = torch::empty({(int64_t)temp_bytes},
-                             keys.options().dtype(torch::kUInt8));
-    runs_sorted_i64(keys.data_ptr<int64_t>(), n,
-                    uniq.data_ptr<int64_t>(), starts.data_ptr<int64_t>(),
-                    count.data_ptr<int64_t>(), temp.data_ptr(),
-                    temp_bytes, current_stream());
+    with_rocprim_temp(keys, [&](void* temp, size_t& temp_bytes) {
+      runs_sorted_i64(keys.data_ptr<int64_t>(), n,
+                      uniq.data_ptr<int64_t>(), starts.data_ptr<int64_t>(),
+                      count.data_ptr<int64_t>(), temp, temp_bytes,
+                      current_stream());
+    });
     return {uniq, starts, count};
   }
   auto stream = current_stream();
@@ -1138,53 +1003,6 @@ torch::Tensor colsum16(torch::Tensor x, bool mfma) {
                        out.data_ptr<float>());
   HIP_CHECK(hipGetLastError());
   return out;
-}
-
-torch::Tensor radix_argsort(torch::Tensor keys) {
-  TORCH_CHECK(keys.is_cuda() && keys.is_contiguous());
-  int64_t n = keys.size(0);
-  auto perm_in = torch::arange(n, keys.options().dtype(torch::kInt64));
-  auto perm_out = torch::empty_like(perm_in);
-  auto keys_out = torch::empty_like(keys);
-  int begin_bit = 0, end_bit = (int)keys.element_size() * 8;
-  if (n > 0 && probed_sortable(keys)) {
-    std::vector<int> passes =
-        keys.scalar_type() == torch::kInt64
-            ? probe_passes<int64_t>(keys) : probe_passes<int32_t>(keys);
-    if (passes.empty()) return perm_in;
-    if (use_hand_path(passes)) {
-      if (keys.scalar_type() == torch::kInt64)
-        hand_radix_sort<int64_t, 1>(keys, perm_in, keys_out, perm_out,
-                                    passes);
-      else
-        hand_radix_sort<int32_t, 1>(keys, perm_in, keys_out, perm_out,
-                                    passes);
-      return perm_out;
-    }
-    begin_bit = passes.front() * 8;
-    end_bit = (passes.back() + 1) * 8;
-  }
-  auto run = [&](auto fn) {
-    size_t temp_bytes = 0;
-    fn(keys.data_ptr(), keys_out.data_ptr(),
-       perm_in.data_ptr<int64_t>(), perm_out.data_ptr<int64_t>(), n,
-       begin_bit, end_bit, nullptr, temp_bytes, current_stream());
-    auto temp = torch::empty({(int64_t)temp_bytes},
-                             keys.options().dtype(torch::kUInt8));
-    fn(keys.data_ptr(), keys_out.data_ptr(),
-       perm_in.data_ptr<int64_t>(), perm_out.data_ptr<int64_t>(), n,
-       begin_bit, end_bit, temp.data_ptr(), temp_bytes,
-       current_stream());
-  };
-  switch (keys.scalar_type()) {
-    case torch::kInt64: run(radix_sort_pairs_int64_t); break;
-    case torch::kInt32: run(radix_sort_pairs_int32_t); break;
-    case torch::kFloat32: run(radix_sort_pairs_float); break;
-    case torch::kFloat64: run(radix_sort_pairs_double); break;
-    default:
-      TORCH_CHECK(false, "radix_argsort: unsupported dtype");
-  }
-  return perm_out;
 }
 
 // K13: one launch of the expression interpreter (expr.hip) over a
@@ -1426,16 +1244,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("GBP_TILE_ROWS") = (int64_t)GBP_TILE_ROWS;
   m.attr("GBP_LDS_SLOTS") = (int64_t)GBP_LDS_SLOTS;
   m.attr("GBP_MAX_BUCKETS") = (int64_t)GBP_MAX_BUCKETS;
-  m.def("groupby_insert_mlp", &groupby_insert_mlp,
-        "multi-row software-pipelined insert (int64 sum)");
-  m.def("groupby_insert_packed_rep", &groupby_insert_packed_rep,
-        "replicated packed insert (fabric-ceiling experiment)");
-  m.def("groupby_insert_packed", &groupby_insert_packed,
-        "packed-slot insert (int64 sum fast path)");
-  m.def("groupby_compact_packed", &groupby_compact_packed,
-        "packed-slot compaction");
-  m.def("alloc_packed_table", &alloc_packed_table,
-        "allocate+init packed table");
   m.def("groupby_compact", &groupby_compact,
         "hash-aggregate table compaction (K9)");
   m.def("agg_identity", &agg_identity, "aggregation identity fill");

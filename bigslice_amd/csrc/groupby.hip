@@ -281,14 +281,9 @@ extern "C" __global__ void k_groupby_insert_sum_i64_lds(
     atomicAdd(global_hits, lds_hits);
 }
 
-// Packed-slot variant for the hottest shape (single int64 value, SUM):
-// slot i = table[2i]=key, table[2i+1]=sum.  Key and accumulator share a
-// 16-byte-aligned pair, so each row touches ONE cache line instead of
-// two — the insert is atomic-latency-bound, so halving touched lines
-// matters.  Table size 2*(cap+1); extra slot for the sentinel key.
-// Partition ids from table-slot high bits (for the partition-first
-// insert experiment: rows whose slots share a table range are inserted
-// together, giving the TCC atomics temporal locality).
+// Partition ids from table-slot high bits: the bucket id of the
+// partitioned insert (groupby_part.hip), whose tests use this kernel
+// as their oracle.
 extern "C" __global__ void k_slot_pids(const int64_t* keys, int64_t n,
                                        int64_t cap, int32_t nparts,
                                        uint32_t seed, int32_t* pids) {
@@ -300,132 +295,6 @@ extern "C" __global__ void k_slot_pids(const int64_t* keys, int64_t n,
   for (; i < n; i += stride) {
     uint64_t h = mm3_u64((uint64_t)keys[i], seed) & mask;
     pids[i] = (int32_t)(h >> shift);
-  }
-}
-
-extern "C" __global__ void k_groupby_insert_packed_sum_i64(
-    const int64_t* keys, const int64_t* vals, int64_t n, int64_t* table,
-    int64_t cap, uint32_t seed, int32_t* sentinel_seen, int32_t* overflow,
-    int64_t max_probes) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  uint64_t mask = (uint64_t)cap - 1;
-  for (; i < n; i += stride) {
-    int64_t k = keys[i];
-    int64_t slot;
-    if (k == GB_SENTINEL) {
-      atomicOr(sentinel_seen, 1);
-      slot = cap;
-    } else {
-      uint64_t h = mm3_u64((uint64_t)k, seed) & mask;
-      int64_t probes = 0;
-      for (;;) {
-        long long cur = ((volatile long long*)table)[2 * h];
-        if (cur == k) break;
-        if (cur == GB_SENTINEL) {
-          long long prev = atomicCAS((unsigned long long*)&table[2 * h],
-                                     (unsigned long long)GB_SENTINEL,
-                                     (unsigned long long)k);
-          if (prev == GB_SENTINEL || prev == k) break;
-        }
-        h = (h + 1) & mask;
-        if (++probes >= max_probes) {
-          atomicOr(overflow, 1);
-          return;
-        }
-      }
-      slot = (int64_t)h;
-    }
-    atomicAdd((unsigned long long*)&table[2 * slot + 1],
-              (unsigned long long)vals[i]);
-  }
-}
-
-// Sub-table replication experiment (NOTES.md item 1 / round-2 task:
-// confirm or refute the fabric/atomic-throughput ceiling): REP
-// replicas of the packed table, block b inserting into replica
-// b % REP (blocks land on XCD b % 8, so replica ~= XCD).  Relieves
-// per-line atomic contention at the cost of REP x the table footprint
-// (pushes a presized table out of the 256 MiB L3).  Merge = compact
-// each replica then re-aggregate (cheap at #distinct rows).
-extern "C" __global__ void k_groupby_insert_packed_rep(
-    const int64_t* keys, const int64_t* vals, int64_t n, int64_t* table,
-    int64_t cap, int32_t nrep, uint32_t seed, int32_t* sentinel_seen,
-    int32_t* overflow, int64_t max_probes) {
-  int64_t* mytab = table + (int64_t)(blockIdx.x % nrep) * 2 * (cap + 1);
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  uint64_t mask = (uint64_t)cap - 1;
-  for (; i < n; i += stride) {
-    int64_t k = keys[i];
-    int64_t slot;
-    if (k == GB_SENTINEL) {
-      atomicOr(sentinel_seen, 1);
-      slot = cap;
-    } else {
-      uint64_t h = mm3_u64((uint64_t)k, seed) & mask;
-      int64_t probes = 0;
-      for (;;) {
-        long long cur = ((volatile long long*)mytab)[2 * h];
-        if (cur == k) break;
-        if (cur == GB_SENTINEL) {
-          long long prev = atomicCAS((unsigned long long*)&mytab[2 * h],
-                                     (unsigned long long)GB_SENTINEL,
-                                     (unsigned long long)k);
-          if (prev == GB_SENTINEL || prev == k) break;
-        }
-        h = (h + 1) & mask;
-        if (++probes >= max_probes) {
-          atomicOr(overflow, 1);
-          return;
-        }
-      }
-      slot = (int64_t)h;
-    }
-    atomicAdd((unsigned long long*)&mytab[2 * slot + 1],
-              (unsigned long long)vals[i]);
-  }
-}
-
-extern "C" __global__ void k_groupby_compact_packed(
-    const int64_t* table, int64_t cap, int64_t slots_per_block,
-    int64_t* out_keys, int64_t* out_vals, unsigned long long* cursor) {
-  __shared__ uint32_t counts[THREADS];
-  __shared__ unsigned long long block_base;
-  int64_t start = (int64_t)blockIdx.x * slots_per_block;
-  int64_t end = min(start + slots_per_block, cap);
-  uint32_t mine = 0;
-  for (int64_t i = start + threadIdx.x; i < end; i += blockDim.x)
-    mine += (table[2 * i] != GB_SENTINEL);
-  counts[threadIdx.x] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t run = 0;
-    for (int t = 0; t < (int)blockDim.x; ++t) {
-      uint32_t c = counts[t];
-      counts[t] = run;
-      run += c;
-    }
-    block_base = run ? atomicAdd(cursor, (unsigned long long)run) : 0;
-  }
-  __syncthreads();
-  int64_t pos = (int64_t)block_base + counts[threadIdx.x];
-  for (int64_t i = start + threadIdx.x; i < end; i += blockDim.x) {
-    int64_t k = table[2 * i];
-    if (k == GB_SENTINEL) continue;
-    out_keys[pos] = k;
-    out_vals[pos] = table[2 * i + 1];
-    ++pos;
-  }
-}
-
-extern "C" __global__ void k_fill_packed_slots(int64_t* table,
-                                               int64_t nslots) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < nslots; i += stride) {
-    table[2 * i] = GB_SENTINEL;
-    table[2 * i + 1] = 0;
   }
 }
 
@@ -470,83 +339,5 @@ extern "C" __global__ void k_groupby_insert(
     }
     for (int c = 0; c < vals.n; ++c)
       accum(vals.tab[c], slot, vals.src[c], i, vals.agg[c]);
-  }
-}
-
-// Resolve one row whose FIRST probe was already loaded (cur0): the MLP
-// insert batches first-probe loads of several rows before resolving,
-// so the random-access latency of the table read is paid R-ways in
-// parallel instead of serially per row.
-__device__ __forceinline__ void gb_resolve_add(
-    int64_t k, long long v, long long cur0, uint64_t h, int64_t* tkeys,
-    long long* tab, uint64_t mask, int64_t cap, uint32_t /*seed*/,
-    int32_t* sentinel_seen, int32_t* overflow, int64_t max_probes) {
-  int64_t slot;
-  if (k == GB_SENTINEL) {
-    atomicOr(sentinel_seen, 1);
-    slot = cap;
-  } else {
-    long long cur = cur0;
-    int64_t probes = 0;
-    for (;;) {
-      if (cur == k) break;
-      if (cur == GB_SENTINEL) {
-        long long prev = atomicCAS((unsigned long long*)&tkeys[h],
-                                   (unsigned long long)GB_SENTINEL,
-                                   (unsigned long long)k);
-        if (prev == GB_SENTINEL || prev == k) break;
-      }
-      h = (h + 1) & mask;
-      if (++probes >= max_probes) {
-        atomicOr(overflow, 1);
-        return;
-      }
-      cur = ((volatile long long*)tkeys)[h];
-    }
-    slot = (int64_t)h;
-  }
-  atomicAdd((unsigned long long*)&tab[slot], (unsigned long long)v);
-}
-
-#define GB_MLP_R 4
-
-// Multi-row software-pipelined one-level insert (single int64 SUM
-// shape): R grid-stride rows per iteration, all R first-probe loads in
-// flight together (NOTES.md headroom item 1).
-extern "C" __global__ void k_groupby_insert_sum_i64_mlp(
-    const int64_t* keys, const int64_t* vals, int64_t n, int64_t* tkeys,
-    long long* tab, int64_t cap, uint32_t seed, int32_t* sentinel_seen,
-    int32_t* overflow, int64_t max_probes) {
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  uint64_t mask = (uint64_t)cap - 1;
-  for (int64_t base = tid; base < n; base += stride * GB_MLP_R) {
-    int64_t k[GB_MLP_R];
-    long long v[GB_MLP_R];
-    uint64_t h[GB_MLP_R];
-    long long cur[GB_MLP_R];
-    bool act[GB_MLP_R];
-#pragma unroll
-    for (int r = 0; r < GB_MLP_R; ++r) {
-      int64_t i = base + (int64_t)r * stride;  // coalesced per r
-      act[r] = i < n;
-      if (act[r]) {
-        k[r] = keys[i];
-        v[r] = vals[i];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < GB_MLP_R; ++r)
-      if (act[r] && k[r] != GB_SENTINEL)
-        h[r] = mm3_u64((uint64_t)k[r], seed) & mask;
-#pragma unroll
-    for (int r = 0; r < GB_MLP_R; ++r)  // R loads in flight
-      if (act[r] && k[r] != GB_SENTINEL)
-        cur[r] = ((volatile long long*)tkeys)[h[r]];
-#pragma unroll
-    for (int r = 0; r < GB_MLP_R; ++r)
-      if (act[r])
-        gb_resolve_add(k[r], v[r], cur[r], h[r], tkeys, tab, mask, cap,
-                       seed, sentinel_seen, overflow, max_probes);
   }
 }

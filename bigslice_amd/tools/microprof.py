@@ -83,12 +83,10 @@ def tokenize_ab(dev, g, iters, nbytes=64 << 20):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("which", choices=["groupby", "groupby_pp", "groupby_part",
-                                      "insert", "insert_rep",
+    ap.add_argument("which", choices=["groupby", "groupby_part", "insert",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
                                       "runs", "tokenize"])
-    ap.add_argument("--nrep", type=int, default=8)
     ap.add_argument("--cap", type=int, default=0,
                     help="table capacity (0 = 2x nkeys rounded up)")
     ap.add_argument("--rows", type=int, default=125_000_000)
@@ -107,39 +105,11 @@ def main():
                          device=dev, generator=g)
     vals = torch.ones(args.rows, dtype=torch.int64, device=dev)
 
-    out = {"which": args.which, "rows": args.rows, "nkeys": args.nkeys,
-           "packed": os.environ.get("BIGSLICE_GB_PACKED", "1")}
+    out = {"which": args.which, "rows": args.rows, "nkeys": args.nkeys}
     if args.which == "groupby":
         def run():
             t = kernels.GroupTable([torch.int64], ["sum"], dev)
             t.insert(keys, [vals])
-            t.finish()
-        ms = timeit(run, args.iters)
-    elif args.which == "groupby_pp":
-        # partition-first: scatter rows by table-slot range, then insert
-        # bucket-by-bucket so atomics have TCC temporal locality
-        P = int(os.environ.get("PP_PARTS", "64"))
-
-        def run():
-            t = kernels.GroupTable([torch.int64], ["sum"], dev)
-            from bigslice_amd import config as cfg
-            cap = 1024
-            while cap < min(2 * keys.shape[0], cfg.GROUPBY_INITIAL_CAP):
-                cap <<= 1
-            t._alloc(cap)
-            pids = kernels._C.slot_pids(keys, cap, P)
-            (rk, rv), counts = kernels._C.scatter_by_partition(
-                [keys, vals], pids, P)
-            off = 0
-            t.rows = keys.shape[0]
-            t._mode = "global"
-            t.batches.append((keys, [vals]))
-            for c in counts.tolist():
-                if c:
-                    kernels._C.groupby_insert(
-                        rk[off:off + c], [rv[off:off + c]], t.codes,
-                        t.tkeys, t.tabs, t.flags, kernels.MAX_PROBES)
-                off += c
             t.finish()
         ms = timeit(run, args.iters)
     elif args.which == "groupby_part":
@@ -220,43 +190,27 @@ def main():
         out["flushed_slots"] = flushed
         args.rows = n
         ms = out["part_ms"]
-    elif args.which in ("insert", "insert_rep"):
-        # steady-state insert throughput into a presized packed table
-        # (all keys present after warmup: pure probe+atomicAdd path);
-        # insert_rep = the sub-table replication experiment
-        cap = args.cap
-        if not cap:
-            cap = 1024
-            while cap < 2 * args.nkeys:
-                cap <<= 1
-        nrep = args.nrep if args.which == "insert_rep" else 1
-        table = kernels._C.alloc_packed_table(
-            cap * nrep + nrep - 1,  # nrep*(cap+1) slots
-            torch.empty(0, dtype=torch.int64, device=dev))
-        flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        out["cap"] = cap
-        out["nrep"] = nrep
-
-        def run():
-            if nrep > 1:
-                kernels._C.groupby_insert_packed_rep(
-                    keys, vals, table, nrep, flags, 4096)
-            else:
-                kernels._C.groupby_insert_packed(
-                    keys, vals, table, flags, 4096)
-        ms = timeit(run, args.iters)
-        assert int(flags[1].item()) == 0, "table overflow"
-    elif args.which == "compact":
+    elif args.which in ("insert", "compact"):
+        # insert: steady-state rate of the plain one-pass insert into a
+        # presized table (all keys present after warmup: pure
+        # probe+atomicAdd); compact: compaction of that filled table
+        cap = args.cap or kernels._next_pow2(2 * args.nkeys)
         t = kernels.GroupTable([torch.int64], ["sum"], dev)
-        t.insert(keys, [vals])
+        t._alloc(cap)
+        out["cap"] = cap
 
-        def run():
+        def insert():
+            kernels._C.groupby_insert(keys, [vals], t.codes, t.tkeys,
+                                      t.tabs, t.flags, 4096)
+
+        def compact():
             cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-            if t._packed:
-                kernels._C.groupby_compact_packed(t.table, cursor)
-            else:
-                kernels._C.groupby_compact(t.tkeys, t.tabs, cursor)
-        ms = timeit(run, args.iters)
+            kernels._C.groupby_compact(t.tkeys, t.tabs, cursor)
+        if args.which == "compact":
+            insert()
+        ms = timeit(insert if args.which == "insert" else compact,
+                    args.iters)
+        assert int(t.flags[1].item()) == 0, "table overflow"
     elif args.which == "runs":
         # K18 run-boundary compaction over sorted keys (PMC target)
         sk = torch.sort(keys).values.contiguous()

@@ -263,23 +263,6 @@ def test_reduce_keys_only_gpu():
     assert sorted(cpu.scan()) == sorted(gpu.scan())
 
 
-def test_packed_groupby_variant(kernels, monkeypatch):
-    # experimental packed-slot layout stays correct
-    monkeypatch.setenv("BIGSLICE_GB_PACKED", "1")
-    keys = torch.randint(0, 5000, (1_000_000,), dtype=torch.int64,
-                         device="cuda:0")
-    vals = torch.randint(0, 100, (1_000_000,), dtype=torch.int64,
-                         device="cuda:0")
-    uk, outs = kernels.groupby(keys, [vals], ["sum"])
-    ref_uk, inv = torch.unique(keys, return_inverse=True)
-    ref = torch.zeros(ref_uk.shape[0], dtype=torch.int64,
-                      device="cuda:0").scatter_reduce_(
-        0, inv, vals, reduce="sum", include_self=False)
-    order = torch.argsort(uk)
-    assert torch.equal(uk[order], ref_uk)
-    assert torch.equal(outs[0][order], ref)
-
-
 def test_forced_lds_and_global_modes(kernels, monkeypatch):
     keys = torch.randint(0, 200, (2_000_000,), dtype=torch.int64,
                          device="cuda:0")
@@ -387,6 +370,30 @@ def test_grouptable_sort_combine_paths(kernels):
         order = torch.argsort(uk)
         assert torch.equal(uk[order], ref_uk), mode
         assert torch.equal(us[order], ref_sum), mode
+
+
+def test_combine_hash_turns_sort_verdict_into_global(kernels, monkeypatch):
+    # near-distinct keys saturate the sample: the verdict is "sort",
+    # which BIGSLICE_GB_COMBINE=hash turns into the plain insert.  One
+    # batch of 2^21 rows is the smallest that triggers the sample.
+    monkeypatch.setenv("BIGSLICE_GB_COMBINE", "hash")
+    n = 1 << 21
+    g = torch.Generator(device="cuda:0").manual_seed(5)
+    k = torch.randint(-2**62, 2**62, (n,), dtype=torch.int64,
+                      device="cuda:0", generator=g)
+    k[-1000:] = k[0]  # repeats, past the sampled prefix
+    v = torch.randint(-100, 100, (n,), dtype=torch.int64, device="cuda:0",
+                      generator=g)
+    t = kernels.GroupTable([torch.int64], ["sum"], torch.device("cuda:0"))
+    t.insert(k, [v])
+    assert t._mode == "pending"
+    uk, (us,) = t.finish()
+    assert t._mode == "global"
+    ref_uk, inv = torch.unique(k, return_inverse=True)
+    ref_sum = torch.zeros_like(ref_uk).index_add_(0, inv, v)
+    order = torch.argsort(uk)
+    assert torch.equal(uk[order], ref_uk)
+    assert torch.equal(us[order], ref_sum)
 
 
 def test_grouptable_mixed_provisional_sort(kernels):
