@@ -25,11 +25,9 @@ for nkeys in (1_000, 1_000_000, 10_000_000):
         return ks2, vs2[0]
 
     def sort_path_k16():
-        from bigslice_amd.kernels import _C
-        ks, vs = kernels.radix_sort_kv(k, v)
-        uq, sums, cnt = _C.segment_sum_sorted(ks, vs)
-        m = int(cnt.item())
-        return uq[:m], sums[:m]
+        from bigslice_amd.kernels.sortedkeys import sort_combine
+        uq, (sums,) = sort_combine(k, [v], [0])
+        return uq, sums
 
     def sort_path():
         ks, vs = kernels.radix_sort_kv(k, v)
@@ -52,8 +50,7 @@ for nkeys in (1_000, 1_000_000, 10_000_000):
     assert torch.equal(hk[ho], sk), nkeys
     assert torch.equal(hv[ho], sv), nkeys
     k16k, k16v = sort_path_k16()
-    o = torch.argsort(k16k)
-    assert torch.equal(k16k[o], sk) and torch.equal(k16v[o], sv), nkeys
+    assert torch.equal(k16k, sk) and torch.equal(k16v, sv), nkeys
     th = timeit(hash_path)
     ts = timeit(sort_path)
     tk = timeit(sort_path_k16)

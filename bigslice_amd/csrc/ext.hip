@@ -851,11 +851,6 @@ std::vector<torch::Tensor> segment_reduce_sorted(torch::Tensor keys,
   return {uniq, aggs, count};
 }
 
-std::vector<torch::Tensor> segment_sum_sorted_i64(torch::Tensor keys,
-                                                  torch::Tensor vals) {
-  return segment_reduce_sorted(keys, vals, 0);
-}
-
 // K16 fast path (runs.hip): int64 segmented reduction over sorted
 // values with precomputed run boundaries.  The caller computes runs
 // once via runs_sorted and reuses them for every value column (the
@@ -1250,8 +1245,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("radix_argsort", &radix_argsort, "device radix argsort (K6)");
   m.def("radix_sort_keys", &radix_sort_keys, "device radix key sort",
         py::arg("keys"), py::arg("probe") = true);
-  m.def("segment_sum_sorted", &segment_sum_sorted_i64,
-        "reduce-by-key sum over sorted int64 pairs (K16)");
   m.def("runs_sorted", &runs_sorted,
         "run boundaries of sorted keys (K18)");
   m.def("segment_reduce_runs", &segment_reduce_runs,

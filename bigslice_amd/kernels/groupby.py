@@ -18,6 +18,7 @@ from typing import List, Optional
 import torch
 
 from . import _C, ALLOW_FALLBACK, _require
+from .sortedkeys import sort_combine
 
 _AGG_CODES = {"sum": 0, "min": 1, "max": 2, "prod": 3}
 
@@ -278,18 +279,14 @@ class GroupTable:
 
     @property
     def _sort_combinable(self) -> bool:
-        """Shapes the sort+reduce-by-key combine handles: sum/min/max
-        over numeric columns.  The segmented reduction is DETERMINISTIC
-        (fixed tree order), so float sums through this path are
-        run-to-run reproducible — unlike the hash table's atomic adds.
-        These shapes defer their batches until a sampled cardinality
-        has chosen the combine mode."""
+        """Shapes sortedkeys.sort_combine handles: sum/min/max over
+        numeric columns (its float sums are run-to-run reproducible —
+        unlike the hash table's atomic adds).  These shapes defer their
+        batches until a sampled cardinality has chosen the combine mode."""
         return (_C is not None
                 and str(self.device).startswith("cuda")
                 and all(a in ("sum", "min", "max") for a in self.aggs)
-                and all(dt in (torch.int64, torch.int32, torch.float32,
-                               torch.float64)
-                        for dt in self.val_dtypes))
+                and all(dt in _GB_VAL_DTYPES for dt in self.val_dtypes))
 
     def _start_sample(self, keys: torch.Tensor) -> None:
         """Cardinality sample: sorted prefix of the first large batch.
@@ -409,52 +406,10 @@ class GroupTable:
                 self._flush_deferred()
                 return None
         self._deferred = []
-        ncols = len(self.val_dtypes)
-        if ncols == 1 and self.val_dtypes[0].itemsize == 8:
-            vals = (batches[0][1][0] if len(batches) == 1
-                    else torch.cat([v[0] for _, v in batches]))
-            ks, vs = _C.radix_sort_kv(keys.contiguous(),
-                                      vals.contiguous())
-            vcols = [vs]
-        else:
-            perm = _C.radix_argsort(keys.contiguous())
-            ks = keys[perm]
-            vcols = []
-            for c in range(ncols):
-                col = (batches[0][1][c] if len(batches) == 1
-                       else torch.cat([v[c] for _, v in batches]))
-                vcols.append(col[perm])
-        # K16: segmented reduction per value column.  Fast path for
-        # int64 columns: boundaries come from ONE k_runs_sorted pass
-        # (reused across columns) and k_segreduce walks each run with
-        # one thread — exact for ints in any order.  Guards: skewed
-        # runs (max length > 4096, one thread would serialize) and
-        # float sums (need reduce_by_key's fixed reduction tree for
-        # run-to-run determinism) take the rocPRIM path.
-        uk = None
-        outs = []
-        runs = None
-        if all(dt == torch.int64 for dt in self.val_dtypes):
-            nrows = ks.shape[0]
-            uq, starts, cnt = _C.runs_sorted(ks.contiguous())
-            guard = _C.runs_guard(starts, cnt, nrows).cpu()  # one sync
-            m, maxlen = int(guard[0]), int(guard[1])
-            if m == 0 or maxlen <= 4096:
-                uk = uq[:m]
-                runs = starts[:m]
-        if runs is not None:
-            for c, v in enumerate(vcols):
-                outs.append(_C.segment_reduce_runs(
-                    v.contiguous(), runs, nrows, self.codes[c]))
-        else:
-            uk = None
-            for c, v in enumerate(vcols):
-                uq, aggs, cnt = _C.segment_reduce_sorted(
-                    ks, v.contiguous(), self.codes[c])
-                if uk is None:
-                    m = int(cnt.item())
-                    uk = uq[:m]
-                outs.append(aggs[:m])
+        vcols = (list(batches[0][1]) if len(batches) == 1
+                 else [torch.cat(cols)
+                       for cols in zip(*(v for _, v in batches))])
+        uk, outs = sort_combine(keys, vcols, self.codes)
         if self.cap is not None:
             # merge with the provisionally hash-inserted batches
             self._insert_now(uk, outs)

@@ -319,15 +319,11 @@ def _combine_once(keys: List[torch.Tensor], vals: List[torch.Tensor],
         vals = list(vals)
     out_vals = []
     for v, a in zip(vals, agg.aggs):
-        init = _scatter_init(a, v.dtype, nseg, v.device)
+        init = torch.empty(nseg, dtype=v.dtype, device=v.device)
         out = init.scatter_reduce_(0, inv, v, reduce=_SCATTER_OP[a],
                                    include_self=False)
         out_vals.append(out)
     return uks, out_vals
-
-
-def _scatter_init(aggname: str, dtype, n: int, device):
-    return torch.empty(n, dtype=dtype, device=device)
 
 
 class DictAggregator:

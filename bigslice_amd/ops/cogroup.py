@@ -94,38 +94,6 @@ def _key_sort(k):
     return k
 
 
-def _runs(sorted_keys):
-    """Run boundaries of a SORTED key array: (unique_keys, starts,
-    ends).  Device int64 path: ONE reduce-by-key pass over a counting
-    iterator (_C.runs_sorted, 8 B/row read); fallback: diff mask +
-    nonzero (3 reads of the key array + a bool-mask round trip)."""
-    import torch
-
-    from .. import kernels
-    n = sorted_keys.shape[0]
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int64,
-                        device=sorted_keys.device)
-        return e, e, e
-    if (sorted_keys.is_cuda and sorted_keys.dtype == torch.int64
-            and kernels.have_extension()):
-        uniq, starts, cnt = kernels._C.runs_sorted(
-            sorted_keys.contiguous())
-        c = int(cnt.item())
-        uniq, starts = uniq[:c], starts[:c]
-    else:
-        mask = torch.empty(n, dtype=torch.bool,
-                           device=sorted_keys.device)
-        mask[0] = True
-        torch.ne(sorted_keys[1:], sorted_keys[:-1], out=mask[1:])
-        starts = mask.nonzero(as_tuple=True)[0]
-        uniq = sorted_keys[starts]
-    ends = torch.cat([starts[1:],
-                      torch.tensor([n], dtype=torch.int64,
-                                   device=sorted_keys.device)])
-    return uniq, starts, ends
-
-
 def _segments_for(run, value_cols, union_keys):
     """Per-value-column SegmentedColumns aligned with union_keys,
     built from the dep's precomputed runs.  Keys the dep lacks get
@@ -149,34 +117,6 @@ def _segments_for(run, value_cols, union_keys):
             for v in value_cols]
 
 
-def _merge_sorted_unique(a, b):
-    """Sorted-unique union of two SORTED key arrays via searchsorted
-    scatter (2 passes; ~3x cheaper than re-sorting the concatenation)."""
-    import torch
-    n, m = a.shape[0], b.shape[0]
-    if n == 0:
-        merged = b
-    elif m == 0:
-        merged = a
-    else:
-        pos_a = torch.arange(n, device=a.device) +             torch.searchsorted(b, a, right=False)
-        pos_b = torch.arange(m, device=a.device) +             torch.searchsorted(a, b, right=True)
-        merged = torch.empty(n + m, dtype=a.dtype, device=a.device)
-        merged[pos_a] = a
-        merged[pos_b] = b
-    from .. import kernels
-    if (merged.is_cuda and merged.dtype == torch.int64
-            and kernels.have_extension() and merged.shape[0] > 0):
-        # one-pass dedup (K18) instead of compare + boolean index
-        # (whose nonzero sync + gather chain costs three passes)
-        uniq, _starts, cnt = kernels._C.runs_sorted(merged.contiguous())
-        return uniq[:int(cnt.item())]
-    mask = torch.ones(merged.shape[0], dtype=torch.bool,
-                      device=merged.device)
-    mask[1:] = merged[1:] != merged[:-1]
-    return merged[mask]
-
-
 # Attach the device generator to Cogroup (kept separate for readability).
 def _cogroup_device_gen(self, dep_readers, ctx):
     import torch
@@ -185,6 +125,7 @@ def _cogroup_device_gen(self, dep_readers, ctx):
 
     from ..sortio import sort_frame
     from .. import kernels
+    from ..kernels.sortedkeys import merge_sorted_unique, runs, unique_sorted
 
     device = ctx.device
     # 1. sort each dep side by key once (direct kv radix for 2-column)
@@ -193,9 +134,9 @@ def _cogroup_device_gen(self, dep_readers, ctx):
         frames = [f for f in r]
         sorted_deps.append(sort_frame(Frame.concat(frames))
                            if frames else None)
-    runs = [(_runs(sd.columns[0].contiguous()) if sd is not None
-             else None) for sd in sorted_deps]
-    uniq_arrays = [r[0] for r in runs if r is not None]
+    dep_runs = [(runs(sd.columns[0].contiguous()) if sd is not None
+                 else None) for sd in sorted_deps]
+    uniq_arrays = [r[0] for r in dep_runs if r is not None]
     if not uniq_arrays:
         return
     # 2. sorted-unique union of the per-dep DISTINCT keys (tiny next
@@ -203,21 +144,15 @@ def _cogroup_device_gen(self, dep_readers, ctx):
     if len(uniq_arrays) == 1:
         union_keys = uniq_arrays[0]
     elif len(uniq_arrays) == 2:
-        union_keys = _merge_sorted_unique(uniq_arrays[0],
-                                          uniq_arrays[1])
+        union_keys = merge_sorted_unique(uniq_arrays[0], uniq_arrays[1])
     else:
-        cat = torch.cat(uniq_arrays)
-        sk = kernels.radix_sort_keys(cat) \
-            if kernels.sort_pairs_supported(cat) else torch.sort(cat).values
-        mask = torch.ones(sk.shape[0], dtype=torch.bool,
-                          device=sk.device)
-        mask[1:] = sk[1:] != sk[:-1]
-        union_keys = sk[mask]
+        union_keys = unique_sorted(
+            kernels.radix_sort_keys(torch.cat(uniq_arrays)))
     # 3. per-dep segments over the sorted values
     out_cols = [union_keys]
     for di, sd in enumerate(sorted_deps):
         if sd is not None:
-            out_cols.extend(_segments_for(runs[di], sd.columns[1:],
+            out_cols.extend(_segments_for(dep_runs[di], sd.columns[1:],
                                           union_keys))
         else:
             empty_vals = [torch.empty(0, dtype=dt, device=device)

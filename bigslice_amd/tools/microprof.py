@@ -233,26 +233,13 @@ def main():
     if ms is not None:
         out["ms"] = ms
         out["grows_per_sec"] = args.rows / ms / 1e6
-    if args.which == "sortcombine":
-        from bigslice_amd.kernels import _C
-
-        def run():
-            ks, vs = _C.radix_sort_kv(keys, vals)
-            uq, sm, cnt = _C.segment_reduce_sorted(ks, vs, 0)
-            int(cnt.item())
-        out["ms"] = timeit(run, args.iters)
-        out["grows_per_s"] = args.rows / out["ms"] / 1e6
-    if args.which == "sortcombine2":
-        # sort + one k_runs boundary pass + thread-per-run segsum
-        from bigslice_amd.kernels import _C
-
-        def run():
-            ks, vs = _C.radix_sort_kv(keys, vals)
-            uq, starts, cnt = _C.runs_sorted(ks)
-            g = _C.runs_guard(starts, cnt, ks.shape[0]).cpu()
-            _C.segment_reduce_runs(vs, starts[:int(g[0])],
-                                   ks.shape[0], 0)
-        out["ms"] = timeit(run, args.iters)
+    if args.which in ("sortcombine", "sortcombine2"):
+        # production sort_combine, one arm forced: sortcombine = rocPRIM
+        # reduce-by-key, sortcombine2 = K18 boundaries + thread-per-run
+        from bigslice_amd.kernels.sortedkeys import sort_combine
+        arm = "rocprim" if args.which == "sortcombine" else "runs"
+        out["ms"] = timeit(
+            lambda: sort_combine(keys, [vals], [0], arm=arm), args.iters)
         out["grows_per_s"] = args.rows / out["ms"] / 1e6
     if args.which == "hashbytes":
         import random

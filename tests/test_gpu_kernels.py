@@ -295,7 +295,7 @@ def test_runs_sorted_matches_fallback(kernels, monkeypatch):
     # K18 one-pass run boundaries vs the diff-mask chain, including
     # all-equal, all-distinct, negative keys and the large-tile
     # geometry (>16M rows); the rocPRIM A/B arm must agree too
-    from bigslice_amd.ops.cogroup import _runs
+    from bigslice_amd.kernels.sortedkeys import runs as _runs
     for keys in (
             torch.randint(0, 97, (1_000_003,), dtype=torch.int64),
             torch.zeros(4097, dtype=torch.int64),
@@ -346,6 +346,102 @@ def test_segment_reduce_runs_fast_path(kernels, monkeypatch):
         ref_max = ref_max[ref_k]
         assert torch.equal(outs[0].cpu()[order], ref_sum), skew
         assert torch.equal(outs[1].cpu()[order], ref_max), skew
+
+
+def _guard_rows(longest):
+    """Sorted int64 keys: one run of `longest` rows and a hundred short
+    ones (under 10k rows), with two int64 value columns."""
+    g = torch.Generator().manual_seed(longest)
+    lens = torch.randint(1, 40, (101,), generator=g)
+    lens[37] = longest
+    keys = torch.repeat_interleave(torch.arange(-50, 51), lens)
+    n = keys.shape[0]
+    assert n < 10_000
+    return keys, [torch.randint(-1000, 1000, (n,), generator=g)
+                  for _ in range(2)]
+
+
+def _count_segreduce_calls(monkeypatch):
+    """Wrap the two K16 reductions; returns the live call counts."""
+    from bigslice_amd.kernels import _C
+    calls = {"segment_reduce_runs": 0, "segment_reduce_sorted": 0}
+    for name in calls:
+        def counted(*args, _name=name, _fn=getattr(_C, name)):
+            calls[_name] += 1
+            return _fn(*args)
+        monkeypatch.setattr(_C, name, counted)
+    return calls
+
+
+def _assert_combined(got, want):
+    assert torch.equal(got[0].cpu(), want[0])
+    assert len(got[1]) == len(want[1])
+    for g, w in zip(got[1], want[1]):
+        assert torch.equal(g.cpu(), w)
+
+
+def test_segment_reduce_guard_boundary(kernels, monkeypatch):
+    # a longest run of SEGREDUCE_MAX_RUN rows still takes the
+    # thread-per-run arm, one row more goes to rocPRIM; both agree with
+    # the module's CPU result
+    from bigslice_amd.kernels.sortedkeys import (SEGREDUCE_MAX_RUN,
+                                                 segment_reduce)
+    assert SEGREDUCE_MAX_RUN == 4096
+    calls = _count_segreduce_calls(monkeypatch)
+    for longest, arm in ((4096, "segment_reduce_runs"),
+                         (4097, "segment_reduce_sorted")):
+        keys, vcols = _guard_rows(longest)
+        want = segment_reduce(keys, vcols, [0, 2])
+        calls.update(segment_reduce_runs=0, segment_reduce_sorted=0)
+        got = segment_reduce(keys.cuda(), [v.cuda() for v in vcols],
+                             [0, 2])
+        _assert_combined(got, want)
+        other = ({"segment_reduce_runs", "segment_reduce_sorted"}
+                 - {arm}).pop()
+        assert calls == {arm: 2, other: 0}, longest
+
+
+def test_segment_reduce_forced_arms_agree(kernels):
+    from bigslice_amd.kernels.sortedkeys import sort_combine
+    keys, vcols = _guard_rows(4096)
+    perm = torch.randperm(keys.shape[0],
+                          generator=torch.Generator().manual_seed(3))
+    keys = keys[perm].cuda()
+    vcols = [v[perm].cuda() for v in vcols]
+    a = sort_combine(keys, vcols, [0, 2], arm="runs")
+    b = sort_combine(keys, vcols, [0, 2], arm="rocprim")
+    assert torch.equal(a[0], b[0])
+    assert torch.equal(a[1][0], b[1][0])
+    assert torch.equal(a[1][1], b[1][1])
+
+
+def test_segment_reduce_float_sum_takes_rocprim(kernels, monkeypatch):
+    # a float32 sum column sends every column to reduce-by-key, whose
+    # fixed reduction tree makes the sums reproducible bit for bit
+    from bigslice_amd.kernels.sortedkeys import segment_reduce
+    g = torch.Generator().manual_seed(9)
+    n = 5000
+    keys = torch.sort(torch.randint(0, 60, (n,), generator=g)).values.cuda()
+    vcols = [torch.rand(n, generator=g).cuda(),
+             torch.randint(-9, 9, (n,), generator=g).cuda()]
+    calls = _count_segreduce_calls(monkeypatch)
+    first = segment_reduce(keys, vcols, [0, 0])
+    second = segment_reduce(keys, vcols, [0, 0])
+    assert calls == {"segment_reduce_runs": 0, "segment_reduce_sorted": 4}
+    assert first[1][0].dtype == torch.float32
+    _assert_combined(second, (first[0].cpu(), [o.cpu() for o in first[1]]))
+    assert torch.equal(first[0].cpu(), torch.unique(keys.cpu()))
+
+
+def test_merge_sorted_unique_device_matches_cpu(kernels):
+    # the device union (K18 dedup) against the CPU one, with an empty
+    # side and with both sides empty
+    from bigslice_amd.kernels.sortedkeys import merge_sorted_unique
+    a = torch.tensor([-4, 1, 3, 9, 12])
+    b = torch.tensor([-7, 1, 2, 9, 10, 30])
+    for x, y in ((a, b), (a, b[:0]), (a[:0], b), (a[:0], b[:0])):
+        got = merge_sorted_unique(x.cuda(), y.cuda())
+        assert torch.equal(got.cpu(), merge_sorted_unique(x, y))
 
 
 def test_grouptable_sort_combine_paths(kernels):
