@@ -24,6 +24,7 @@
 #include "strings.hip"
 #include "expr.hip"
 #include "tokenize.hip"
+#include "groupby_multi.hip"
 
 namespace {
 
@@ -526,6 +527,155 @@ std::vector<torch::Tensor> groupby_compact(torch::Tensor tkeys,
                      (unsigned long long*)cursor.data_ptr());
   HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// ------------------------------------------- multi-column group-by (K21)
+
+// Launch one of the k_gbm_* kernels at the instantiation for nk key
+// columns: 2, 3 and 4 have their own, the rest take the generic one.
+#define GBM_LAUNCH(kernel, nk, blocks, ...)                              \
+  do {                                                                   \
+    switch (nk) {                                                        \
+      case 2:                                                            \
+        hipLaunchKernelGGL(kernel<2>, dim3(blocks), dim3(THREADS), 0,    \
+                           current_stream(), __VA_ARGS__);               \
+        break;                                                           \
+      case 3:                                                            \
+        hipLaunchKernelGGL(kernel<3>, dim3(blocks), dim3(THREADS), 0,    \
+                           current_stream(), __VA_ARGS__);               \
+        break;                                                           \
+      case 4:                                                            \
+        hipLaunchKernelGGL(kernel<4>, dim3(blocks), dim3(THREADS), 0,    \
+                           current_stream(), __VA_ARGS__);               \
+        break;                                                           \
+      default:                                                           \
+        hipLaunchKernelGGL(kernel<0>, dim3(blocks), dim3(THREADS), 0,    \
+                           current_stream(), __VA_ARGS__);               \
+    }                                                                    \
+    HIP_CHECK(hipGetLastError());                                        \
+  } while (0)
+
+uint64_t gbm_fp_mask(int64_t fp_bits) {
+  TORCH_CHECK(fp_bits >= 1 && fp_bits <= 64, "fp_bits must be in [1, 64]");
+  return fp_bits == 64 ? ~uint64_t(0) : (uint64_t(1) << fp_bits) - 1;
+}
+
+// The batch side of MkCols: 2..MAX_KEY_COLS contiguous int64 device
+// columns of one length, which is returned.
+int64_t gbm_batch_keys(MkCols& kc, const std::vector<torch::Tensor>& keys) {
+  TORCH_CHECK(keys.size() >= 2 && (int)keys.size() <= MAX_KEY_COLS,
+              "2..", MAX_KEY_COLS, " key columns supported");
+  kc.n = (int)keys.size();
+  const int64_t n = keys[0].size(0);
+  for (size_t c = 0; c < keys.size(); ++c) {
+    TORCH_CHECK(keys[c].is_cuda() && keys[c].is_contiguous() &&
+                    keys[c].scalar_type() == torch::kInt64 &&
+                    keys[c].dim() == 1 && keys[c].size(0) == n,
+                "key columns must be contiguous int64 device tensors of "
+                "one length");
+    kc.src[c] = keys[c].data_ptr<int64_t>();
+    kc.tab[c] = nullptr;
+  }
+  return n;
+}
+
+// The table side: tags int64[cap+1], one int64[cap+1] array per key
+// column, flags int32[3] = {unused, overflow, collision}.  Returns cap.
+int64_t gbm_table(MkCols& kc, const torch::Tensor& tags,
+                  const std::vector<torch::Tensor>& kcols,
+                  at::ArrayRef<torch::Tensor> tabs,
+                  const torch::Tensor& flags) {
+  const int64_t cap = table_cap(tags, tabs, flags);
+  // a row's slot travels between the launches as a uint32, all-ones
+  // meaning "none"
+  TORCH_CHECK(cap <= (int64_t(1) << 31), "capacity above 2^31");
+  TORCH_CHECK(flags.numel() >= 3, "flags must be int32[3]");
+  TORCH_CHECK((int)kcols.size() == kc.n, "one key array per key column");
+  for (size_t c = 0; c < kcols.size(); ++c) {
+    TORCH_CHECK(kcols[c].is_cuda() && kcols[c].is_contiguous() &&
+                kcols[c].scalar_type() == torch::kInt64 &&
+                kcols[c].dim() == 1 && kcols[c].size(0) == cap + 1);
+    kc.tab[c] = kcols[c].data_ptr<int64_t>();
+  }
+  return cap;
+}
+
+int gbm_blocks(int64_t n) {
+  return (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
+}
+
+// The device tag of every row (tests compare it with the torch mirror,
+// kernels/groupby_multi.fingerprint64).
+torch::Tensor groupby_mk_fingerprint(std::vector<torch::Tensor> keys,
+                                     int64_t fp_bits) {
+  MkCols kc{};
+  const int64_t n = gbm_batch_keys(kc, keys);
+  const uint64_t fp_mask = gbm_fp_mask(fp_bits);
+  auto out = torch::empty({n}, keys[0].options());
+  if (n == 0) return out;
+  GBM_LAUNCH(k_gbm_fingerprint, kc.n, gbm_blocks(n), kc, n, GB_HASH_SEED,
+             fp_mask, out.data_ptr<int64_t>());
+  return out;
+}
+
+// Launch 1: claim slots by tag; returns each row's slot (uint32 bits in
+// an int32 tensor, -1 = none: the probe chain overflowed).
+torch::Tensor groupby_mk_claim(std::vector<torch::Tensor> keys,
+                               torch::Tensor tags,
+                               std::vector<torch::Tensor> kcols,
+                               torch::Tensor flags, int64_t max_probes,
+                               int64_t fp_bits) {
+  MkCols kc{};
+  const int64_t n = gbm_batch_keys(kc, keys);
+  const int64_t cap = gbm_table(kc, tags, kcols, {}, flags);
+  const uint64_t fp_mask = gbm_fp_mask(fp_bits);
+  TORCH_CHECK(max_probes >= 1);
+  auto slots = torch::empty({n}, keys[0].options().dtype(torch::kInt32));
+  if (n == 0) return slots;
+  GBM_LAUNCH(k_gbm_claim, kc.n, gbm_blocks(n), kc, n,
+             tags.data_ptr<int64_t>(), cap, GB_HASH_SEED, fp_mask,
+             (uint32_t*)slots.data_ptr<int32_t>(),
+             flags.data_ptr<int32_t>() + 1, max_probes);
+  return slots;
+}
+
+// Launch 2: compare the stored tuple and accumulate.  slots must come
+// from groupby_mk_claim on the same table and batch.
+void groupby_mk_accum(std::vector<torch::Tensor> keys,
+                      std::vector<torch::Tensor> vals,
+                      std::vector<int64_t> aggs, torch::Tensor slots,
+                      torch::Tensor tags, std::vector<torch::Tensor> kcols,
+                      std::vector<torch::Tensor> tabs,
+                      torch::Tensor flags) {
+  MkCols kc{};
+  const int64_t n = gbm_batch_keys(kc, keys);
+  const int64_t cap = gbm_table(kc, tags, kcols, tabs, flags);
+  TORCH_CHECK(keys.size() + vals.size() <= (size_t)MAX_COLS,
+              "at most ", MAX_COLS, " key and value columns");
+  TORCH_CHECK(slots.is_cuda() && slots.is_contiguous() &&
+              slots.scalar_type() == torch::kInt32 && slots.dim() == 1 &&
+              slots.size(0) == n);
+  ValCols vc = make_val_cols(vals, tabs, aggs);
+  for (const auto& v : vals)
+    TORCH_CHECK(v.dim() == 1 && v.size(0) == n,
+                "value columns must have one entry per row");
+  if (n == 0) return;
+  GBM_LAUNCH(k_gbm_accum, kc.n, gbm_blocks(n), kc, n, vc,
+             (const uint32_t*)slots.data_ptr<int32_t>(), cap,
+             flags.data_ptr<int32_t>() + 2);
+}
+
+// Streaming insert of one batch: both launches on the current stream.
+// Nothing is read back; the host reads flags after compaction.
+void groupby_mk_insert(std::vector<torch::Tensor> keys,
+                       std::vector<torch::Tensor> vals,
+                       std::vector<int64_t> aggs, torch::Tensor tags,
+                       std::vector<torch::Tensor> kcols,
+                       std::vector<torch::Tensor> tabs, torch::Tensor flags,
+                       int64_t max_probes, int64_t fp_bits) {
+  auto slots = groupby_mk_claim(keys, tags, kcols, flags, max_probes,
+                                fp_bits);
+  groupby_mk_accum(keys, vals, aggs, slots, tags, kcols, tabs, flags);
 }
 
 // ---------------------------------------------------------------- sort
@@ -1241,6 +1391,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("GBP_MAX_BUCKETS") = (int64_t)GBP_MAX_BUCKETS;
   m.def("groupby_compact", &groupby_compact,
         "hash-aggregate table compaction (K9)");
+  m.def("groupby_mk_insert", &groupby_mk_insert,
+        "multi-column-key hash-aggregate insert: claim + accumulate (K21)",
+        py::arg("keys"), py::arg("vals"), py::arg("aggs"), py::arg("tags"),
+        py::arg("kcols"), py::arg("tabs"), py::arg("flags"),
+        py::arg("max_probes"), py::arg("fp_bits") = 64);
+  m.def("groupby_mk_claim", &groupby_mk_claim,
+        "launch 1 of groupby_mk_insert; returns the rows' slots");
+  m.def("groupby_mk_accum", &groupby_mk_accum,
+        "launch 2 of groupby_mk_insert");
+  m.def("groupby_mk_fingerprint", &groupby_mk_fingerprint,
+        "the tuple fingerprint groupby_mk_insert claims slots by",
+        py::arg("keys"), py::arg("fp_bits") = 64);
+  m.attr("MAX_KEY_COLS") = (int64_t)MAX_KEY_COLS;
+  m.attr("MAX_COLS") = (int64_t)MAX_COLS;
   m.def("agg_identity", &agg_identity, "aggregation identity fill");
   m.def("radix_argsort", &radix_argsort, "device radix argsort (K6)");
   m.def("radix_sort_keys", &radix_sort_keys, "device radix key sort",

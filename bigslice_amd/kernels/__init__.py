@@ -96,6 +96,10 @@ from .groupby import (  # noqa: E402,F401
     GroupTable, _next_pow2, groupby, groupby_supported, part_buckets,
     part_owned_buckets)
 
+# -- group-by aggregate over multi-column integer keys (K21) ---------------
+
+from .groupby_multi import MultiKeyTable, fingerprint64  # noqa: E402,F401
+
 
 # -- sort (K6) -------------------------------------------------------------
 

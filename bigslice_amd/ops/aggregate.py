@@ -9,6 +9,9 @@ row-wise open-addressing table with whole-batch device aggregation:
   (csrc/groupby.hip) using an HBM open-addressing table with LDS
   pre-aggregation per workgroup; torch scatter_reduce is the portable
   fallback (and the CPU path).
+* 2..8 int64/int32 key columns + numeric values: a HIP table keyed by the
+  whole tuple (csrc/groupby_multi.hip); other numeric composite keys and
+  the CPU path use a lexicographic sort + segment reduce.
 * arbitrary keys/values/fns: a host dict accumulator (the reference's
   accum.go path).
 
@@ -155,10 +158,12 @@ class BytesKeyAggregator:
 class TensorAggregator:
     """Device/CPU aggregation for numeric key column(s).
 
-    Single int64 keys on GPU stream through the HIP GroupTable;
-    everything else combines via sort-based segment reduce (multi-column
-    keys use a lexicographic sort + boundary detection).  State is
-    re-compacted on flush, bounding memory at O(distinct keys).
+    Single int64 keys on GPU stream through the HIP GroupTable, and
+    tuples of 2..8 int64/int32 key columns through the HIP MultiKeyTable
+    (BIGSLICE_GB_MULTIKEY=0 turns that off); everything else combines
+    via sort-based segment reduce (multi-column keys use a lexicographic
+    sort + boundary detection).  State is re-compacted on flush,
+    bounding memory at O(distinct keys).
     """
 
     def __init__(self, schema: Schema, agg: Aggregation, device: str):
@@ -193,6 +198,21 @@ class TensorAggregator:
                 kernels._require("groupby")  # no silent eager fallback
             if shape_ok and kernels.have_extension():
                 self._table = kernels.GroupTable(val_dts, agg.aggs, device)
+        elif device.startswith("cuda") and self.nkey >= 2:
+            from .. import kernels
+            from ..kernels import groupby_multi as gbm
+            val_dts = schema.dtypes[schema.prefix:]
+            shape_ok = (gbm.multikey_supported(
+                schema.dtypes[:schema.prefix], val_dts, agg.aggs)
+                and gbm.Options.from_env().enabled)
+            if shape_ok and not kernels.have_extension() and \
+                    not kernels.ALLOW_FALLBACK:
+                kernels._require("groupby")  # no silent eager fallback
+            if shape_ok and kernels.have_extension():
+                # two tuples with one fingerprint: regroup exactly
+                self._table = gbm.MultiKeyTable(
+                    self.nkey, val_dts, agg.aggs, device,
+                    fallback=lambda k, v: _combine_once(k, v, self.agg))
 
     # small device batches are concatenated before insert: one launch
     # instead of many (consumer-side shuffle buckets are ~100k rows)
@@ -224,8 +244,7 @@ class TensorAggregator:
                 if self._pending_rows >= 4 * self._SMALL_ROWS:
                     self._flush_table_pending()
                 return
-            self._table.insert(frame.columns[0].contiguous(),
-                               [c.contiguous() for c in frame.columns[1:]])
+            self._table_insert(frame)
             return
         self._pending.append(frame)
         self._pending_rows += len(frame)
@@ -238,8 +257,14 @@ class TensorAggregator:
         f = Frame.concat(self._pending)
         self._pending.clear()
         self._pending_rows = 0
-        self._table.insert(f.columns[0].contiguous(),
-                           [c.contiguous() for c in f.columns[1:]])
+        self._table_insert(f)
+
+    def _table_insert(self, f: Frame) -> None:
+        vals = [c.contiguous() for c in f.columns[self.nkey:]]
+        if self.nkey == 1:
+            self._table.insert(f.columns[0].contiguous(), vals)
+        else:
+            self._table.insert(list(f.columns[:self.nkey]), vals)
 
     def _flush(self) -> None:
         if not self._pending:
@@ -263,8 +288,9 @@ class TensorAggregator:
         if self._table is not None:
             self._flush_table_pending()
             keys, vals = self._table.finish()
-            if keys.shape[0]:
-                self.keys, self.vals = [keys], vals
+            keys = [keys] if self.nkey == 1 else keys
+            if keys[0].shape[0]:
+                self.keys, self.vals = keys, vals
         else:
             self._flush()
         if self.keys is None:

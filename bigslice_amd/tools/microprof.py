@@ -4,6 +4,7 @@
   python -m bigslice_amd.tools.microprof partition --rows 125000000
   python -m bigslice_amd.tools.microprof hash --rows 125000000
   python -m bigslice_amd.tools.microprof tokenize --iters 20
+  python -m bigslice_amd.tools.microprof groupby_multi --rows 8388608
 
 Times each kernel phase with hipEvents over --iters iterations.  Keep
 runs short: this is the target for `rocprofv3 --pmc ... -- ...`.
@@ -81,9 +82,59 @@ def tokenize_ab(dev, g, iters, nbytes=64 << 20):
     return out
 
 
+def groupby_multi(dev, g, iters, rows, nkeys, ncols, cap):
+    """The two launches of the multi-column insert (K21), each on its
+    own, over one batch into a presized warm table (every tuple present
+    after the warmups: pure probe / compare + atomicAdd), then the whole
+    insert and the table's compaction."""
+    from bigslice_amd.kernels import groupby_multi as gbm
+    C = kernels._C
+    # tuples: mixed-radix digits of a number below nkeys
+    ids = torch.randint(0, nkeys, (rows,), dtype=torch.int64, device=dev,
+                        generator=g)
+    radix = int(round(nkeys ** (1.0 / ncols))) + 1
+    keys = [((ids // radix ** c) % radix).contiguous()
+            for c in range(ncols)]
+    del ids
+    vals = [torch.ones(rows, dtype=torch.int64, device=dev)]
+    t = gbm.MultiKeyTable(ncols, [torch.int64], ["sum"], dev)
+    t._alloc(cap or kernels._next_pow2(4 * nkeys))
+    fp = t.opts.fp_bits
+    out = {"which": "groupby_multi", "rows": rows, "nkeys": nkeys,
+           "key_cols": ncols, "cap": t.cap}
+    slots = C.groupby_mk_claim(keys, t.tags, t.kcols, t.flags,
+                               kernels.MAX_PROBES, fp)
+    out["claim_ms"] = timeit(
+        lambda: C.groupby_mk_claim(keys, t.tags, t.kcols, t.flags,
+                                   kernels.MAX_PROBES, fp), iters)
+    out["accum_ms"] = timeit(
+        lambda: C.groupby_mk_accum(keys, vals, t.codes, slots, t.tags,
+                                   t.kcols, t.tabs, t.flags), iters)
+    out["insert_ms"] = timeit(
+        lambda: C.groupby_mk_insert(keys, vals, t.codes, t.tags, t.kcols,
+                                    t.tabs, t.flags, kernels.MAX_PROBES,
+                                    fp), iters)
+
+    def compact():
+        cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+        C.groupby_compact(t.tags, t.kcols + t.tabs, cursor)
+    out["compact_ms"] = timeit(compact, iters)
+    flags = t.flags.tolist()
+    assert flags[1] == 0 and flags[2] == 0, flags
+    out["distinct"] = int((t.tags[:t.cap] != kernels.GB_SENTINEL).sum())
+    # streamed bytes per row: K key columns read by both launches, the
+    # slot written and read, the value column read
+    stream = rows * (2 * 8 * ncols + 2 * 4 + 8)
+    out["insert_stream_gbps"] = stream / out["insert_ms"] / 1e6
+    out["accum_gatomics_per_s"] = rows / out["accum_ms"] / 1e6
+    out["grows_per_sec"] = rows / out["insert_ms"] / 1e6
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", choices=["groupby", "groupby_part", "insert",
+                                      "groupby_multi",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
                                       "runs", "tokenize"])
@@ -92,6 +143,8 @@ def main():
     ap.add_argument("--rows", type=int, default=125_000_000)
     ap.add_argument("--nkeys", type=int, default=1_000_000)
     ap.add_argument("--nparts", type=int, default=8)
+    ap.add_argument("--key-cols", type=int, default=2,
+                    help="key columns of groupby_multi")
     ap.add_argument("--iters", type=int, default=3)
     args = ap.parse_args()
     assert torch.cuda.is_available() and kernels.have_extension()
@@ -100,6 +153,11 @@ def main():
     g.manual_seed(1)
     if args.which == "tokenize":
         print(json.dumps(tokenize_ab(dev, g, args.iters)))
+        return
+    if args.which == "groupby_multi":
+        print(json.dumps(groupby_multi(dev, g, args.iters, args.rows,
+                                       args.nkeys, args.key_cols,
+                                       args.cap)))
         return
     keys = torch.randint(0, args.nkeys, (args.rows,), dtype=torch.int64,
                          device=dev, generator=g)
