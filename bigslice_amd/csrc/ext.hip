@@ -4,6 +4,8 @@
 //   scatter_by_partition
 //   groupby           (K9 hash-aggregate)
 //   radix_argsort     (K6 device radix sort)
+//   runs_multi /      (K22 run boundaries and lexicographic search over
+//   lex_searchsorted   multi-column keys)
 //
 // Single translation unit: the kernel files are included directly.
 
@@ -20,6 +22,7 @@
 #include "sort.hip"
 #include "radix.hip"
 #include "runs.hip"
+#include "runs_multi.hip"
 #include "vecagg.hip"
 #include "strings.hip"
 #include "expr.hip"
@@ -1093,6 +1096,104 @@ std::vector<torch::Tensor> runs_sorted(torch::Tensor keys) {
   return {uniq, starts, count};
 }
 
+// ------------------------------ multi-column sorted-key primitives (K22)
+
+// Launch one of the runs_multi.hip kernels at the instantiation for nk
+// key columns: 2, 3 and 4 have their own, the rest take the generic one.
+#define MRUNS_LAUNCH(kernel, nk, blocks, threads, ...)                    \
+  do {                                                                    \
+    switch (nk) {                                                         \
+      case 2:                                                             \
+        hipLaunchKernelGGL(kernel<2>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+        break;                                                            \
+      case 3:                                                             \
+        hipLaunchKernelGGL(kernel<3>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+        break;                                                            \
+      case 4:                                                             \
+        hipLaunchKernelGGL(kernel<4>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+        break;                                                            \
+      default:                                                            \
+        hipLaunchKernelGGL(kernel<0>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+    }                                                                     \
+    HIP_CHECK(hipGetLastError());                                         \
+  } while (0)
+
+// 1..MAX_KEY_COLS contiguous int64 device columns of one length on one
+// device; returns the length.
+int64_t lex_cols(const std::vector<torch::Tensor>& cols, const char* what) {
+  TORCH_CHECK(!cols.empty() && (int)cols.size() <= MAX_KEY_COLS, what,
+              ": 1..", MAX_KEY_COLS, " key columns supported");
+  const int64_t n = cols[0].size(0);
+  for (const auto& c : cols)
+    TORCH_CHECK(c.is_cuda() && c.is_contiguous() &&
+                    c.scalar_type() == torch::kInt64 && c.dim() == 1 &&
+                    c.size(0) == n && c.device() == cols[0].device(),
+                what, ": key columns must be contiguous int64 device "
+                "tensors of one length");
+  return n;
+}
+
+// (distinct tuples per column, run starts, count) of lexicographically
+// SORTED key columns: count, scan and write on the current stream
+// (runs_multi.hip).  The outputs hold n entries; count is a 1-element
+// device tensor and the caller slices after one readback.
+std::tuple<std::vector<torch::Tensor>, torch::Tensor, torch::Tensor>
+runs_multi(std::vector<torch::Tensor> cols) {
+  const int64_t n = lex_cols(cols, "runs_multi");
+  MrCols kc{};
+  kc.n = (int)cols.size();
+  std::vector<torch::Tensor> uniq;
+  for (int c = 0; c < kc.n; ++c) {
+    uniq.push_back(torch::empty_like(cols[c]));
+    kc.src[c] = cols[c].data_ptr<int64_t>();
+    kc.uniq[c] = uniq[c].data_ptr<int64_t>();
+  }
+  auto starts = torch::empty_like(cols[0]);
+  if (n == 0) return {uniq, starts, torch::zeros({1}, cols[0].options())};
+  const int64_t ntiles = (n + MRUNS_TILE - 1) / MRUNS_TILE;
+  TORCH_CHECK(ntiles < (1ll << 31), "runs_multi: batch too large");
+  auto counts = torch::empty({ntiles}, cols[0].options());
+  MRUNS_LAUNCH(k_mruns_count, kc.n, (uint32_t)ntiles, MRUNS_BLOCK, kc, n,
+               counts.data_ptr<int64_t>());
+  // 1-D on purpose: a 2-D cumsum over dim 0 takes torch's strided
+  // outer-dim scan (see tokenize_bytes)
+  auto incl = at::cumsum(counts, 0);
+  MRUNS_LAUNCH(k_mruns_write, kc.n, (uint32_t)ntiles, MRUNS_BLOCK, kc, n,
+               (const int64_t*)incl.data_ptr<int64_t>(), n,
+               starts.data_ptr<int64_t>());
+  return {uniq, starts, incl.slice(0, ntiles - 1, ntiles)};
+}
+
+// Lower (right = false) or upper bound of every query tuple among
+// lexicographically SORTED tuples, torch.searchsorted's meaning.
+// Nothing is read back.
+torch::Tensor lex_searchsorted(std::vector<torch::Tensor> sorted_cols,
+                               std::vector<torch::Tensor> query_cols,
+                               bool right) {
+  const int64_t u = lex_cols(sorted_cols, "lex_searchsorted");
+  const int64_t m = lex_cols(query_cols, "lex_searchsorted");
+  TORCH_CHECK(sorted_cols.size() == query_cols.size() &&
+                  sorted_cols[0].device() == query_cols[0].device(),
+              "lex_searchsorted: sorted and query tuples must have the "
+              "same columns on one device");
+  LexCols kc{};
+  kc.n = (int)sorted_cols.size();
+  for (int c = 0; c < kc.n; ++c) {
+    kc.sorted[c] = sorted_cols[c].data_ptr<int64_t>();
+    kc.query[c] = query_cols[c].data_ptr<int64_t>();
+  }
+  auto out = torch::empty({m}, query_cols[0].options());
+  if (m == 0) return out;
+  const int blocks = (int)std::min<int64_t>((m + 255) / 256, 32768);
+  MRUNS_LAUNCH(k_lex_search, kc.n, blocks, 256, kc, u, m, (int)right,
+               out.data_ptr<int64_t>());
+  return out;
+}
+
 // K17: murmur3 over variable-length byte rows (device strings).
 torch::Tensor hash_bytes(torch::Tensor bytes, torch::Tensor offsets,
                          int64_t seed) {
@@ -1411,6 +1512,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keys"), py::arg("probe") = true);
   m.def("runs_sorted", &runs_sorted,
         "run boundaries of sorted keys (K18)");
+  m.def("runs_multi", &runs_multi,
+        "run boundaries of lexicographically sorted key columns (K22)");
+  m.attr("MRUNS_TILE_ROWS") = (int64_t)MRUNS_TILE;
+  m.def("lex_searchsorted", &lex_searchsorted,
+        "searchsorted over lexicographically sorted tuples (K22)",
+        py::arg("sorted_cols"), py::arg("query_cols"),
+        py::arg("right") = false);
   m.def("segment_reduce_runs", &segment_reduce_runs,
         "int64 segmented reduce with precomputed runs (K16 fast path)");
   m.def("runs_guard", &runs_guard,

@@ -1,5 +1,6 @@
 """Operations on key-sorted arrays: run boundaries (K18), the
-sorted-unique merge, and the sort-combine pipeline (K6 sort + K16
+sorted-unique merge, their multi-column forms with a lexicographic
+sort and search (K22), and the sort-combine pipeline (K6 sort + K16
 segmented reduction).
 
 Every function takes and returns torch tensors.  A device tensor goes to
@@ -69,6 +70,118 @@ def merge_sorted_unique(a, b):
     merged[pos_a] = a
     merged[pos_b] = b
     return unique_sorted(merged)
+
+
+# -- multi-column keys (K22) ------------------------------------------------
+#
+# A key is a tuple of integer columns, first column most significant.
+# The extension takes contiguous int64 columns: int32 columns are widened
+# on the way in and narrowed on the way out, as MultiKeyTable does.
+
+# rows per tile of the run-boundary kernels (csrc/runs_multi.hip)
+MRUNS_TILE_ROWS = _C.MRUNS_TILE_ROWS if _C is not None else 4096
+
+
+def _wide(cols):
+    return [c.to(torch.int64).contiguous() for c in cols]
+
+
+def lex_argsort(cols):
+    """Stable permutation sorting the rows of `cols` lexicographically:
+    one stable sort per column from the last to the first (device: the
+    radix argsort, stable on both of its engines; CPU: torch.sort)."""
+    cols = list(cols)
+    native = _native(cols[0], "lex_argsort")
+    perm = None
+    for c in reversed(cols):
+        k = c if perm is None else c[perm]
+        if native:
+            o = _C.radix_argsort(k.contiguous())
+        else:
+            o = torch.sort(k, stable=True).indices
+        perm = o if perm is None else perm[o]
+    return perm
+
+
+def _uniq_starts_multi(sorted_cols):
+    """([distinct tuples per column], run_starts) of lexicographically
+    SORTED columns of n > 0 rows, one readback."""
+    n = sorted_cols[0].shape[0]
+    if _native(sorted_cols[0], "runs_multi"):
+        uniq, starts, cnt = _C.runs_multi(_wide(sorted_cols))
+        c = int(cnt.item())
+        return ([u[:c] if s.dtype == torch.int64 else u[:c].to(s.dtype)
+                 for u, s in zip(uniq, sorted_cols)], starts[:c])
+    mask = torch.zeros(n, dtype=torch.bool, device=sorted_cols[0].device)
+    mask[0] = True
+    for c in sorted_cols:
+        mask[1:] |= c[1:] != c[:-1]
+    starts = mask.nonzero(as_tuple=True)[0]
+    return [c[starts] for c in sorted_cols], starts
+
+
+def runs_multi(sorted_cols):
+    """(unique tuple columns, starts, ends) of the runs of
+    lexicographically SORTED key columns."""
+    sorted_cols = list(sorted_cols)
+    n, dev = sorted_cols[0].shape[0], sorted_cols[0].device
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int64, device=dev)
+        return [c[:0] for c in sorted_cols], e, e
+    uniq, starts = _uniq_starts_multi(sorted_cols)
+    ends = torch.cat([starts[1:],
+                      torch.tensor([n], dtype=torch.int64, device=dev)])
+    return uniq, starts, ends
+
+
+def unique_sorted_multi(sorted_cols):
+    """The distinct tuples of lexicographically SORTED columns, in order,
+    one tensor per column."""
+    return runs_multi(sorted_cols)[0]
+
+
+def lex_searchsorted(sorted_cols, query_cols, right=False):
+    """torch.searchsorted over tuples: for every query tuple, the first
+    position among the lexicographically SORTED tuples whose tuple is
+    >= the query (right=False) or > the query (right=True).  int64[m]."""
+    sorted_cols, query_cols = _wide(sorted_cols), _wide(query_cols)
+    if len(sorted_cols) != len(query_cols):
+        raise ValueError("sorted and query tuples differ in width")
+    if _native(query_cols[0], "lex_searchsorted"):
+        return _C.lex_searchsorted(sorted_cols, query_cols, bool(right))
+    # Dense lexicographic ranks of all tuples, then the scalar search:
+    # equal tuples share a rank and the sorted side's ranks are sorted.
+    u = sorted_cols[0].shape[0]
+    both = [torch.cat([s, q]) for s, q in zip(sorted_cols, query_cols)]
+    perm = lex_argsort(both)
+    ordered = [c[perm] for c in both]
+    step = torch.zeros(perm.shape[0], dtype=torch.int64,
+                       device=perm.device)
+    for c in ordered:
+        step[1:] |= (c[1:] != c[:-1]).to(torch.int64)
+    rank = torch.empty_like(step)
+    rank[perm] = torch.cumsum(step, 0)
+    return torch.searchsorted(rank[:u].contiguous(), rank[u:].contiguous(),
+                              right=bool(right))
+
+
+def merge_sorted_unique_multi(a_cols, b_cols):
+    """Sorted-unique union of two lexicographically SORTED tuple sets:
+    merge_sorted_unique's searchsorted scatter, over tuples."""
+    a_cols, b_cols = list(a_cols), list(b_cols)
+    n, m = a_cols[0].shape[0], b_cols[0].shape[0]
+    dev = a_cols[0].device
+    pos_a = (torch.arange(n, device=dev)
+             + lex_searchsorted(b_cols, a_cols, right=False))
+    pos_b = (torch.arange(m, device=dev)
+             + lex_searchsorted(a_cols, b_cols, right=True))
+    merged = []
+    for a, b in zip(a_cols, b_cols):
+        mc = torch.empty(n + m, dtype=a.dtype, device=dev)
+        mc[pos_a] = a
+        mc[pos_b] = b
+        merged.append(mc)
+    return unique_sorted_multi(merged)
 
 
 def sort_pairs(keys, vcols):

@@ -9,10 +9,13 @@ Two paths:
 * device path (numeric single-key inputs): sort + merge by key on device;
   grouped values surface as list columns on readback.  The heavy join work
   (sort, boundary detection) runs in HIP/rocPRIM via frame sort kernels.
+  Keys of 2 to 8 int64/int32 columns take the same steps over tuples
+  (K22): lexicographic sort, tuple run boundaries, tuple searchsorted.
 """
 
 from __future__ import annotations
 
+import os
 from typing import List
 
 from ..frame import Frame
@@ -54,6 +57,13 @@ class Cogroup(Slice):
                 and all(dt != OBJECT
                         for d in self.deps for dt in d.slice.schema.dtypes)):
             return IterReader(self._device_gen(dep_readers, ctx))
+        # Same path over a composite integer key (K22): lexicographic
+        # sort, tuple run boundaries and a tuple searchsorted.
+        # BIGSLICE_COGROUP_MULTIKEY=0 keeps such keys on the host path.
+        if (ctx.device != "cpu"
+                and os.environ.get("BIGSLICE_COGROUP_MULTIKEY", "1") != "0"
+                and self._multikey_eligible()):
+            return IterReader(self._device_multi_gen(dep_readers, ctx))
 
         def gen():
             # Group each dep by key on the host: key -> [lists per column]
@@ -88,6 +98,31 @@ class Cogroup(Slice):
                             [[row[vi] for row in g[di]] for _, g in part])
                 yield Frame.from_lists(out_cols, schema=self.schema)
         return IterReader(gen())
+
+    def _multikey_eligible(self) -> bool:
+        """Shapes the composite-key device path takes on a GPU session:
+        2..MAX_KEY_COLS int64/int32 key columns and dense torch columns
+        otherwise.  A missing extension is an error there, unless the
+        eager fallback is allowed; then the host path runs."""
+        import torch
+
+        from .. import kernels
+        from ..kernels.groupby_multi import MAX_KEY_COLS
+        nkey = self.schema.prefix
+        if not 2 <= nkey <= MAX_KEY_COLS:
+            return False
+        for d in self.deps:
+            dts = d.slice.schema.dtypes
+            if not all(dt in (torch.int64, torch.int32)
+                       for dt in dts[:nkey]):
+                return False
+            if not all(isinstance(dt, torch.dtype) for dt in dts[nkey:]):
+                return False
+        if not kernels.have_extension():
+            if not kernels.ALLOW_FALLBACK:
+                kernels._require("cogroup over multi-column keys")
+            return False
+        return True
 
 
 def _key_sort(k):
@@ -167,3 +202,81 @@ def _cogroup_device_gen(self, dep_readers, ctx):
 
 
 Cogroup._device_gen = _cogroup_device_gen
+
+
+def _segments_for_multi(run, value_cols, union_cols):
+    """_segments_for over tuple keys: the dep's runs scatter to their
+    positions among the union's tuples, found by lex_searchsorted."""
+    import torch
+
+    from ..frame import SegmentedColumn
+    from ..kernels.sortedkeys import lex_searchsorted
+
+    uniq_cols, starts, ends = run
+    u = union_cols[0].shape[0]
+    if uniq_cols[0].shape[0] != u:
+        # a subset of the union, in the same order (see _segments_for)
+        dev = union_cols[0].device
+        idx = lex_searchsorted(union_cols, uniq_cols)
+        s = torch.zeros(u, dtype=torch.int64, device=dev)
+        e = torch.zeros(u, dtype=torch.int64, device=dev)
+        s[idx] = starts
+        e[idx] = ends
+        starts, ends = s, e
+    return [SegmentedColumn(v.contiguous(), starts, ends)
+            for v in value_cols]
+
+
+def _cogroup_device_multi_gen(self, dep_readers, ctx):
+    """_cogroup_device_gen, step by step, for a key of nkey columns."""
+    import torch
+
+    from ..frame import Frame, SegmentedColumn
+    from ..kernels.sortedkeys import (lex_argsort, merge_sorted_unique_multi,
+                                      runs_multi, unique_sorted_multi)
+
+    device = ctx.device
+    nkey = self.schema.prefix
+    # 1. sort each dep side lexicographically by its key columns once
+    sorted_deps = []
+    for r in dep_readers:
+        frames = [f for f in r if len(f)]
+        if not frames:
+            sorted_deps.append(None)
+            continue
+        f = Frame.concat(frames)
+        sorted_deps.append(f.select(lex_argsort(f.columns[:nkey])))
+    dep_runs = [(runs_multi(sd.columns[:nkey]) if sd is not None else None)
+                for sd in sorted_deps]
+    uniq_tuples = [r[0] for r in dep_runs if r is not None]
+    if not uniq_tuples:
+        return
+    # 2. sorted-unique union of the per-dep DISTINCT tuples
+    if len(uniq_tuples) == 1:
+        union_cols = uniq_tuples[0]
+    elif len(uniq_tuples) == 2:
+        union_cols = merge_sorted_unique_multi(uniq_tuples[0],
+                                               uniq_tuples[1])
+    else:
+        cat = [torch.cat(cs) for cs in zip(*uniq_tuples)]
+        perm = lex_argsort(cat)
+        union_cols = unique_sorted_multi([c[perm] for c in cat])
+    # 3. per-dep segments over the sorted values
+    u = union_cols[0].shape[0]
+    out_cols = list(union_cols)
+    for di, sd in enumerate(sorted_deps):
+        if sd is not None:
+            out_cols.extend(_segments_for_multi(
+                dep_runs[di], sd.columns[nkey:], union_cols))
+        else:
+            empty_vals = [torch.empty(0, dtype=dt, device=device)
+                          for dt in self.deps[di].slice.schema.dtypes[nkey:]]
+            zeros = torch.zeros(u, dtype=torch.int64, device=device)
+            out_cols.extend(SegmentedColumn(ev, zeros, zeros)
+                            for ev in empty_vals)
+    frame = Frame(out_cols, prefix=nkey)
+    for off in range(0, len(frame), ctx.chunk):
+        yield frame.slice(off, min(off + ctx.chunk, len(frame)))
+
+
+Cogroup._device_multi_gen = _cogroup_device_multi_gen

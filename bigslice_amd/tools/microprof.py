@@ -5,6 +5,7 @@
   python -m bigslice_amd.tools.microprof hash --rows 125000000
   python -m bigslice_amd.tools.microprof tokenize --iters 20
   python -m bigslice_amd.tools.microprof groupby_multi --rows 8388608
+  python -m bigslice_amd.tools.microprof runs_multi --rows 8388608
 
 Times each kernel phase with hipEvents over --iters iterations.  Keep
 runs short: this is the target for `rocprofv3 --pmc ... -- ...`.
@@ -131,10 +132,52 @@ def groupby_multi(dev, g, iters, rows, nkeys, ncols, cap):
     return out
 
 
+def runs_multi(dev, g, iters, rows, nkeys, ncols):
+    """The K22 primitives on one warm batch: run boundaries of `rows`
+    lexicographically sorted tuples over about `nkeys` distinct ones
+    (count + scan + write, no readback), beside k_runs_sorted on one
+    column of the same length, and the lexicographic search of nkeys
+    query tuples into the distinct tuples, beside torch.searchsorted on
+    scalars of the same sizes."""
+    C = kernels._C
+    ids = torch.sort(torch.randint(0, nkeys, (rows,), dtype=torch.int64,
+                                   device=dev, generator=g)).values
+    radix = int(round(nkeys ** (1.0 / ncols))) + 1
+    # mixed-radix digits, most significant first: sorted as tuples
+    cols = [((ids // radix ** (ncols - 1 - c)) % radix).contiguous()
+            for c in range(ncols)]
+    out = {"which": "runs_multi", "rows": rows, "nkeys": nkeys,
+           "key_cols": ncols}
+    uniq, starts, cnt = C.runs_multi(cols)
+    u = int(cnt.item())
+    ref = torch.unique_consecutive(ids)
+    assert u == ref.shape[0], (u, ref.shape[0])
+    out["distinct"] = u
+    out["runs_multi_ms"] = timeit(lambda: C.runs_multi(cols), iters)
+    out["runs_sorted_1col_ms"] = timeit(lambda: C.runs_sorted(ids), iters)
+    # the keys are read twice: 2 x NK x 8 B per row
+    out["runs_multi_gbps"] = (rows * 2 * ncols * 8
+                              / out["runs_multi_ms"] / 1e6)
+    out["runs_sorted_1col_gbps"] = rows * 8 / out["runs_sorted_1col_ms"] / 1e6
+    table = [x[:u].contiguous() for x in uniq]
+    pick = torch.randint(0, u, (nkeys,), dtype=torch.int64, device=dev,
+                         generator=g)
+    query = [t[pick].contiguous() for t in table]
+    query[-1] = query[-1] + torch.randint(0, 2, (nkeys,), dtype=torch.int64,
+                                          device=dev, generator=g)
+    out["queries"] = nkeys
+    out["lex_search_ms"] = timeit(
+        lambda: C.lex_searchsorted(table, query, False), iters)
+    q1 = ref[pick].contiguous()
+    out["torch_searchsorted_1col_ms"] = timeit(
+        lambda: torch.searchsorted(ref, q1), iters)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", choices=["groupby", "groupby_part", "insert",
-                                      "groupby_multi",
+                                      "groupby_multi", "runs_multi",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
                                       "runs", "tokenize"])
@@ -144,7 +187,7 @@ def main():
     ap.add_argument("--nkeys", type=int, default=1_000_000)
     ap.add_argument("--nparts", type=int, default=8)
     ap.add_argument("--key-cols", type=int, default=2,
-                    help="key columns of groupby_multi")
+                    help="key columns of groupby_multi and runs_multi")
     ap.add_argument("--iters", type=int, default=3)
     args = ap.parse_args()
     assert torch.cuda.is_available() and kernels.have_extension()
@@ -158,6 +201,10 @@ def main():
         print(json.dumps(groupby_multi(dev, g, args.iters, args.rows,
                                        args.nkeys, args.key_cols,
                                        args.cap)))
+        return
+    if args.which == "runs_multi":
+        print(json.dumps(runs_multi(dev, g, args.iters, args.rows,
+                                    args.nkeys, args.key_cols)))
         return
     keys = torch.randint(0, args.nkeys, (args.rows,), dtype=torch.int64,
                          device=dev, generator=g)

@@ -1,0 +1,148 @@
+"""Multi-column sorted-key operations (K22), torch implementations.
+
+The contract the device path is held to: lex_argsort, runs_multi,
+unique_sorted_multi, lex_searchsorted and merge_sorted_unique_multi on
+CPU tensors against Python oracles (sorted() over tuples,
+itertools.groupby, bisect), never the code under test."""
+
+import bisect
+import itertools
+
+import pytest
+import torch
+
+from bigslice_amd.kernels import sortedkeys as sk
+
+INT64_MIN = -(1 << 63)
+INT64_MAX = (1 << 63) - 1
+
+# rows every random case is extended by: extremes adjacent in each
+# column, rows differing only in the last column, rows differing only in
+# the first while the last repeats, and exact duplicates
+EDGE_ROWS = [
+    (INT64_MIN, 0), (INT64_MAX, 0), (0, INT64_MIN), (0, INT64_MAX),
+    (INT64_MIN, INT64_MIN), (INT64_MAX, INT64_MAX),
+    (7, 1), (7, 2), (7, 3),
+    (1, 5), (2, 5), (3, 5),
+    (-4, -4), (-4, -4), (-4, -4),
+]
+
+
+def _rows(n, ncols, hi, seed):
+    g = torch.Generator().manual_seed(seed)
+    t = torch.randint(-hi, hi, (n, ncols), dtype=torch.int64, generator=g)
+    rows = [tuple(r) for r in t.tolist()]
+    rows += [e + (e[-1],) * (ncols - 2) for e in EDGE_ROWS]
+    return rows
+
+
+def _cols(rows, ncols, dtypes=None):
+    dtypes = dtypes or [torch.int64] * ncols
+    if not rows:
+        return [torch.empty(0, dtype=dt) for dt in dtypes]
+    return [torch.tensor([r[c] for r in rows], dtype=dt)
+            for c, dt in enumerate(dtypes)]
+
+
+def _tuples(cols):
+    return list(zip(*[c.tolist() for c in cols]))
+
+
+CASES = [(300, 2, 6, 1), (400, 3, 4, 2), (257, 5, 2, 3), (64, 8, 2, 4)]
+
+
+@pytest.mark.parametrize("n,ncols,hi,seed", CASES)
+def test_lex_argsort_is_the_stable_tuple_sort(n, ncols, hi, seed):
+    rows = _rows(n, ncols, hi, seed)
+    perm = sk.lex_argsort(_cols(rows, ncols))
+    want = sorted(range(len(rows)), key=lambda i: rows[i])  # stable
+    assert perm.dtype == torch.int64
+    assert perm.tolist() == want
+
+
+def test_lex_argsort_takes_int32_and_keeps_duplicate_order():
+    # few distinct leading values: equal tuples keep their input order
+    rows = [(i % 3, (i // 3) % 2) for i in range(200)]
+    cols = _cols(rows, 2, [torch.int32, torch.int64])
+    perm = sk.lex_argsort(cols)
+    assert perm.tolist() == sorted(range(len(rows)), key=lambda i: rows[i])
+
+
+@pytest.mark.parametrize("n,ncols,hi,seed", CASES)
+def test_runs_multi_matches_groupby(n, ncols, hi, seed):
+    rows = sorted(_rows(n, ncols, hi, seed))
+    uniq, starts, ends = sk.runs_multi(_cols(rows, ncols))
+    want_u, want_s, off = [], [], 0
+    for k, grp in itertools.groupby(rows):
+        want_u.append(k)
+        want_s.append(off)
+        off += len(list(grp))
+    assert _tuples(uniq) == want_u
+    assert starts.tolist() == want_s
+    assert ends.tolist() == want_s[1:] + [len(rows)]
+    assert starts.dtype == ends.dtype == torch.int64
+    assert _tuples(sk.unique_sorted_multi(_cols(rows, ncols))) == want_u
+
+
+def test_runs_multi_edges():
+    e, s, t = sk.runs_multi(_cols([], 2))
+    assert [c.shape[0] for c in e] == [0, 0]
+    assert s.shape[0] == t.shape[0] == 0
+    one = sk.runs_multi(_cols([(3, 4)], 2))
+    assert _tuples(one[0]) == [(3, 4)]
+    assert one[1].tolist() == [0] and one[2].tolist() == [1]
+    same = sk.runs_multi(_cols([(3, 4)] * 9, 2))
+    assert same[1].tolist() == [0] and same[2].tolist() == [9]
+    # (1,5),(2,5): a flag taken from the last column alone would miss it
+    first = sk.runs_multi(_cols([(1, 5), (2, 5)], 2))
+    assert first[1].tolist() == [0, 1]
+    # an int32 column keeps its dtype
+    u, _, _ = sk.runs_multi(_cols([(1, 5), (1, 6)], 2,
+                                  [torch.int32, torch.int64]))
+    assert [c.dtype for c in u] == [torch.int32, torch.int64]
+
+
+@pytest.mark.parametrize("right", [False, True])
+@pytest.mark.parametrize("n,ncols,hi,seed", CASES)
+def test_lex_searchsorted_matches_bisect(n, ncols, hi, seed, right):
+    srt = sorted(_rows(n, ncols, hi, seed))
+    # present, absent, duplicated, below everything and above everything
+    qs = _rows(n // 2, ncols, hi + 1, seed + 100) + srt[::7] + srt[::7]
+    qs += [(INT64_MIN,) * ncols, (INT64_MAX,) * ncols]
+    got = sk.lex_searchsorted(_cols(srt, ncols), _cols(qs, ncols),
+                              right=right)
+    fn = bisect.bisect_right if right else bisect.bisect_left
+    assert got.dtype == torch.int64
+    assert got.tolist() == [fn(srt, q) for q in qs]
+
+
+def test_lex_searchsorted_edges():
+    q = _cols([(1, 2), (-5, 0)], 2)
+    assert sk.lex_searchsorted(_cols([], 2), q).tolist() == [0, 0]
+    assert sk.lex_searchsorted(_cols([], 2), q, right=True).tolist() == [0, 0]
+    one = _cols([(1, 2)], 2)
+    assert sk.lex_searchsorted(one, q).tolist() == [0, 0]
+    assert sk.lex_searchsorted(one, q, right=True).tolist() == [1, 0]
+    assert sk.lex_searchsorted(one, _cols([], 2)).shape[0] == 0
+    # ties in the first column decided by the last; negatives sort first
+    srt = _cols([(-3, 9), (4, 1), (4, 3), (4, 5)], 2)
+    got = sk.lex_searchsorted(srt, _cols([(4, 0), (4, 3), (4, 4), (4, 6),
+                                          (-3, 10), (-4, 0)], 2))
+    assert got.tolist() == [1, 2, 3, 4, 1, 0]
+
+
+@pytest.mark.parametrize("n,ncols,hi,seed", CASES)
+def test_merge_sorted_unique_multi_is_the_set_union(n, ncols, hi, seed):
+    a = sorted(set(_rows(n, ncols, hi, seed)))
+    b = sorted(set(_rows(n // 2, ncols, hi, seed + 50)))
+    got = sk.merge_sorted_unique_multi(_cols(a, ncols), _cols(b, ncols))
+    assert _tuples(got) == sorted(set(a) | set(b))
+
+
+def test_merge_sorted_unique_multi_disjoint_and_equal():
+    a = [(1, 1), (1, 3), (5, 0)]
+    b = [(0, 9), (1, 2), (7, 7)]
+    got = sk.merge_sorted_unique_multi(_cols(a, 2), _cols(b, 2))
+    assert _tuples(got) == sorted(a + b)
+    same = sk.merge_sorted_unique_multi(_cols(a, 2), _cols(a, 2))
+    assert _tuples(same) == a
