@@ -329,39 +329,59 @@ void groupby_insert_lds(torch::Tensor keys, torch::Tensor vals,
   HIP_CHECK(hipGetLastError());
 }
 
+// Tiles per group of the partitioned insert (groupby_part.hip): the
+// histogram and the scatter run one workgroup per group of G consecutive
+// tiles.  G is the smallest value that leaves at most GBP_GROUP_WGS
+// workgroups (two per CU of a 256-CU chip, what the scatter's LDS lets be
+// resident at once), capped at GBP_MAX_GROUP: 1 up to 2M rows, 4 at 8M.
+constexpr int64_t GBP_GROUP_WGS = 512;
+constexpr int64_t GBP_MAX_GROUP = 8;
+
+int64_t part_group_tiles(int64_t n) {
+  const int64_t ntiles = (n + GBP_SCATTER_ROWS - 1) / GBP_SCATTER_ROWS;
+  const int64_t g = (ntiles + GBP_GROUP_WGS - 1) / GBP_GROUP_WGS;
+  return std::min(std::max(g, (int64_t)1), GBP_MAX_GROUP);
+}
+
 // Partitioned LDS pre-aggregation (single int64 SUM value): see
 // groupby_part.hip.  Histogram, offsets and scatter; returns the
 // partitioned (key, value) pairs [n, 2] and the rows per bucket.
+// group_tiles: G, 0 = part_group_tiles(rows).
 std::tuple<torch::Tensor, torch::Tensor> part_scatter_impl(
     const torch::Tensor& keys, const torch::Tensor& vals, int64_t cap,
-    int64_t nbuckets) {
+    int64_t nbuckets, int64_t group_tiles) {
   int64_t n = keys.size(0);
   TORCH_CHECK(n > 0 && n < (int64_t(1) << 31), "1 <= rows < 2^31");
+  TORCH_CHECK(group_tiles >= 0 && group_tiles <= 65536,
+              "0 <= group_tiles <= 65536");
   const uint32_t shift = bucket_shift(cap, nbuckets);
   const uint32_t seed = GB_HASH_SEED;
   const uint32_t mask = (uint32_t)(cap - 1);
   const uint32_t nb = (uint32_t)nbuckets;
   const int64_t ntiles = (n + GBP_SCATTER_ROWS - 1) / GBP_SCATTER_ROWS;
+  const int64_t G = group_tiles ? group_tiles : part_group_tiles(n);
+  const int64_t ngroups = (ntiles + G - 1) / G;
   auto opts32 = keys.options().dtype(torch::kInt32);
-  auto hist = torch::empty({ntiles * nbuckets}, opts32);
+  auto gsum = torch::empty({ngroups * nbuckets}, opts32);
   auto totals = torch::empty({nbuckets}, opts32);
   auto pairs = torch::empty({n, 2}, keys.options());
   auto stream = current_stream();
-  hipLaunchKernelGGL(k_gbp_hist, dim3((uint32_t)ntiles), dim3(GBP_THREADS),
-                     0, stream, keys.data_ptr<int64_t>(), n, nb, seed, mask,
-                     shift, (uint32_t*)hist.data_ptr<int32_t>());
+  hipLaunchKernelGGL(k_gbp_hist, dim3((uint32_t)ngroups), dim3(GBP_THREADS),
+                     0, stream, keys.data_ptr<int64_t>(), n, ntiles,
+                     (uint32_t)G, nb, seed, mask, shift,
+                     (uint32_t*)gsum.data_ptr<int32_t>());
   HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_gbp_offsets, dim3((nb + 63) / 64),
                      dim3(GBP_OFF_THREADS), 0, stream,
-                     (uint32_t*)hist.data_ptr<int32_t>(), ntiles, nb,
+                     (uint32_t*)gsum.data_ptr<int32_t>(), ngroups, nb,
                      (uint32_t*)totals.data_ptr<int32_t>());
   HIP_CHECK(hipGetLastError());
-  const int64_t per_xcd = (ntiles + 7) / 8;
+  const int64_t per_xcd = (ngroups + 7) / 8;
   hipLaunchKernelGGL(k_gbp_scatter, dim3((uint32_t)(8 * per_xcd)),
                      dim3(GBP_THREADS), 0, stream,
                      keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
-                     ntiles, nb, seed, mask, shift,
-                     (const uint32_t*)hist.data_ptr<int32_t>(),
+                     ntiles, (uint32_t)G, ngroups, nb, seed, mask, shift,
+                     (const uint32_t*)gsum.data_ptr<int32_t>(),
                      (const uint32_t*)totals.data_ptr<int32_t>(),
                      (GbPair*)pairs.data_ptr<int64_t>());
   HIP_CHECK(hipGetLastError());
@@ -442,10 +462,12 @@ torch::Tensor part_owned_impl(const torch::Tensor& pairs,
 
 // owned != 0: bucket-owning aggregate (needs capacity / nbuckets <=
 // GBP_LDS_SLOTS); owned == 0: the tiled aggregate with its global flush.
+// group_tiles: scatter tiles per workgroup, 0 = part_group_tiles(rows).
 void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
                          torch::Tensor tkeys, torch::Tensor tab,
                          torch::Tensor flags, int64_t max_probes,
-                         int64_t nbuckets, int64_t owned) {
+                         int64_t nbuckets, int64_t owned,
+                         int64_t group_tiles) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   TORCH_CHECK(vals.scalar_type() == torch::kInt64 &&
               vals.size(0) == keys.size(0));
@@ -454,7 +476,7 @@ void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
   vals = vals.contiguous();
   if (keys.size(0) == 0) return;
   int64_t cap = table_cap(tkeys, {tab}, flags);
-  auto parts = part_scatter_impl(keys, vals, cap, nbuckets);
+  auto parts = part_scatter_impl(keys, vals, cap, nbuckets, group_tiles);
   const torch::Tensor& pairs = std::get<0>(parts);
   if (owned)
     part_owned_impl(pairs, std::get<1>(parts), tkeys, tab, flags,
@@ -467,12 +489,12 @@ void groupby_insert_part(torch::Tensor keys, torch::Tensor vals,
 // bucket [nbuckets]).
 std::tuple<torch::Tensor, torch::Tensor> groupby_part_scatter(
     torch::Tensor keys, torch::Tensor vals, int64_t cap,
-    int64_t nbuckets) {
+    int64_t nbuckets, int64_t group_tiles) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   TORCH_CHECK(vals.scalar_type() == torch::kInt64 &&
               vals.size(0) == keys.size(0));
   return part_scatter_impl(keys.contiguous(), vals.contiguous(), cap,
-                           nbuckets);
+                           nbuckets, group_tiles);
 }
 
 // Aggregate pass alone over already partitioned pairs (kernel timing).
@@ -1479,12 +1501,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "partitioned LDS pre-aggregating insert (single i64 sum)",
         py::arg("keys"), py::arg("vals"), py::arg("tkeys"), py::arg("tab"),
         py::arg("flags"), py::arg("max_probes"), py::arg("nbuckets"),
-        py::arg("owned") = 0);
+        py::arg("owned") = 0, py::arg("group_tiles") = 0);
   m.def("groupby_part_owned", &groupby_part_owned,
         "owner + cleanup passes of the partitioned insert; returns clean");
   m.attr("GBP_OWN_LIMIT") = (int64_t)GBP_OWN_LIMIT;
   m.def("groupby_part_scatter", &groupby_part_scatter,
-        "bucket scatter of the partitioned insert");
+        "bucket scatter of the partitioned insert", py::arg("keys"),
+        py::arg("vals"), py::arg("cap"), py::arg("nbuckets"),
+        py::arg("group_tiles") = 0);
+  m.def("groupby_part_group_tiles", &part_group_tiles,
+        "tiles per group the partitioned insert picks for n rows");
+  m.attr("GBP_SCATTER_ROWS") = (int64_t)GBP_SCATTER_ROWS;
   m.def("groupby_part_aggregate", &groupby_part_aggregate,
         "aggregate pass of the partitioned insert");
   m.attr("GBP_TILE_ROWS") = (int64_t)GBP_TILE_ROWS;

@@ -7,12 +7,18 @@
 // table can absorb them and only ONE global atomic per distinct key per
 // tile reaches the table:
 //
-//   1. k_gbp_hist     per-tile LDS histogram of bucket ids -> tiles x B
+//   1. k_gbp_hist     one workgroup per GROUP of G consecutive 4096-row
+//                     tiles: LDS histogram of the group's bucket ids ->
+//                     groups x B
 //   2. k_gbp_offsets  column-wise exclusive scan of that matrix (in
 //                     place) + per-bucket totals
-//   3. k_gbp_scatter  re-reads the tile, reorders it by bucket in LDS and
+//   3. k_gbp_scatter  one workgroup per group: bucket starts (scan of the
+//                     totals) + its row of the matrix = a cursor per
+//                     bucket, kept by the workgroup.  Tile by tile it
+//                     re-reads the rows, reorders them by bucket in LDS,
 //                     writes (key, value) as 16-byte pairs, each bucket's
-//                     rows of the tile as one contiguous run
+//                     rows of the tile as one contiguous run at the
+//                     cursor, and advances the cursor by the tile's count
 //   4. k_gbp_aggregate fixed tiles of the partitioned buffer -> LDS hash
 //                     table (LDS CAS + 64-bit LDS add) -> one
 //                     gb_global_insert_sum per occupied LDS slot
@@ -26,6 +32,11 @@
 // sentinel slot and the overflow flag are exactly those of groupby.hip:
 // the LDS tables are private pre-aggregators only, and batches inserted
 // by this path and by k_groupby_insert mix freely in one table.
+//
+// The bookkeeping is per group, not per tile: the matrix has tiles / G
+// rows and the scatter never reads a per-tile offset.  G comes from the
+// host (part_group_tiles in ext.hip: about two workgroups per CU, 1 for a
+// 2M-row batch, 4 at 8M rows).
 //
 // No kernel waits on another workgroup; ordering is by launch.
 
@@ -59,30 +70,106 @@ __device__ __forceinline__ uint32_t gbp_bucket(long long k, uint32_t seed,
   return (mm3_u64((uint64_t)k, seed) & mask) >> shift;
 }
 
-extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_hist(
-    const int64_t* keys, int64_t n, uint32_t nb, uint32_t seed,
-    uint32_t mask, uint32_t shift, uint32_t* hist) {
-  __shared__ uint32_t lh[GBP_MAX_BUCKETS];
-  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) lh[b] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * GBP_SCATTER_ROWS;
+// Tiles [t0, t1) of group g (G consecutive scatter tiles), clipped to the
+// batch.
+__device__ __forceinline__ void gbp_group_tiles(int64_t g, uint32_t G,
+                                                int64_t ntiles, int64_t* t0,
+                                                int64_t* t1) {
+  *t0 = g * G;
+  *t1 = min(*t0 + (int64_t)G, ntiles);
+}
+
+// Row of a tile (or histogram chunk) that register j of a thread holds.
+// WIDE: a thread takes two adjacent rows per 16-byte load (the column
+// must be 16-byte aligned; tiles start at even rows), else one row per
+// load.
+template <bool WIDE>
+__device__ __forceinline__ uint32_t gbp_row(int j) {
+  return WIDE ? (j >> 1) * 2 * GBP_THREADS + 2 * threadIdx.x + (j & 1)
+              : j * GBP_THREADS + threadIdx.x;
+}
+
+// R rows of a column starting at row r (a multiple of the tile), rows
+// below r1 only.
+template <bool WIDE, int R>
+__device__ __forceinline__ void gbp_load_rows(const int64_t* col, int64_t r,
+                                              int64_t r1, long long (&x)[R]) {
+  if constexpr (WIDE) {
 #pragma unroll
-  for (int j = 0; j < GBP_SCATTER_ROWS / GBP_THREADS; ++j) {
-    const int64_t i = base + j * GBP_THREADS + threadIdx.x;
-    if (i < n) atomicAdd(&lh[gbp_bucket(keys[i], seed, mask, shift)], 1u);
+    for (int j = 0; j < R; j += 2) {
+      const int64_t i = r + gbp_row<true>(j);
+      if (i + 1 < r1) {
+        const longlong2 two = *(const longlong2*)(col + i);
+        x[j] = two.x;
+        x[j + 1] = two.y;
+      } else if (i < r1) {
+        x[j] = col[i];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int64_t i = r + gbp_row<false>(j);
+      if (i < r1) x[j] = col[i];
+    }
   }
+}
+
+// keys per thread of one histogram chunk (one tile); the next chunk is
+// in flight while the current one goes through the LDS atomics
+#define GBP_HIST_C (GBP_SCATTER_ROWS / GBP_THREADS)
+
+template <bool WIDE>
+__device__ __forceinline__ void gbp_hist_rows(const int64_t* keys, int64_t r0,
+                                              int64_t r1, uint32_t seed,
+                                              uint32_t mask, uint32_t shift,
+                                              uint32_t* lh) {
+  constexpr int64_t CH = (int64_t)GBP_HIST_C * GBP_THREADS;
+  long long k[GBP_HIST_C], kn[GBP_HIST_C];
+  gbp_load_rows<WIDE>(keys, r0, r1, k);
+  __syncthreads();  // lh is cleared
+  for (int64_t r = r0; r < r1; r += CH) {
+    const bool more = r + CH < r1;
+    if (more) gbp_load_rows<WIDE>(keys, r + CH, r1, kn);
+#pragma unroll
+    for (int j = 0; j < GBP_HIST_C; ++j) {
+      if (r + gbp_row<WIDE>(j) < r1)
+        atomicAdd(&lh[gbp_bucket(k[j], seed, mask, shift)], 1u);
+    }
+    if (more) {
+#pragma unroll
+      for (int j = 0; j < GBP_HIST_C; ++j) k[j] = kn[j];
+    }
+  }
+}
+
+// One workgroup per group: all tiles of the group go into one LDS
+// histogram, written as one row gsum[group][b].
+extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_hist(
+    const int64_t* keys, int64_t n, int64_t ntiles, uint32_t G, uint32_t nb,
+    uint32_t seed, uint32_t mask, uint32_t shift, uint32_t* gsum) {
+  __shared__ uint32_t lh[GBP_MAX_BUCKETS];
+  int64_t t0, t1;
+  gbp_group_tiles(blockIdx.x, G, ntiles, &t0, &t1);
+  const int64_t r0 = t0 * GBP_SCATTER_ROWS;
+  const int64_t r1 = min(t1 * GBP_SCATTER_ROWS, n);
+  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) lh[b] = 0;
+  if (((uintptr_t)keys & 15) == 0)
+    gbp_hist_rows<true>(keys, r0, r1, seed, mask, shift, lh);
+  else
+    gbp_hist_rows<false>(keys, r0, r1, seed, mask, shift, lh);
   __syncthreads();
-  uint32_t* row = hist + (int64_t)blockIdx.x * nb;
+  uint32_t* row = gsum + (int64_t)blockIdx.x * nb;
   for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) row[b] = lh[b];
 }
 
-// In-place exclusive scan down each bucket column of the tiles x B
-// matrix, plus the column totals.  One workgroup per 64 adjacent columns
-// (a wave reads 64 consecutive counters of one tile: coalesced); its 16
-// waves split the tile axis, exchange chunk sums through LDS, then
-// rewrite their chunk.  Loads are issued in groups of 8 before the
-// dependent stores so a chunk costs ~tiles/128 round trips, not
-// tiles/16.
+// In-place exclusive scan down each bucket column of the groups x B
+// matrix (ntiles = its rows), plus the column totals.  One workgroup per
+// 64 adjacent columns (a wave reads 64 consecutive counters of one row:
+// coalesced); its 16 waves split the row axis, exchange chunk sums
+// through LDS, then rewrite their chunk.  Loads are issued in groups of 8
+// before the dependent stores so a chunk costs ~rows/128 round trips, not
+// rows/16.
 #define GBP_OFF_THREADS 1024
 #define GBP_OFF_WAVES (GBP_OFF_THREADS / 64)
 
@@ -150,72 +237,154 @@ __device__ __forceinline__ void gbp_block_scan(uint32_t* a, uint32_t nb,
   __syncthreads();
 }
 
-// hist holds the scanned matrix (offset of the tile's run inside each
-// bucket), totals the rows per bucket.  Consecutive tiles are mapped to
-// workgroups 8 apart so neighbouring runs of a bucket are written
-// through the same XCD's L2 and merge into whole lines there.
+// The scan of one tile inside k_gbp_scatter.  lstart[b] = rows of bucket
+// b in the tile -> their start in the staged tile, as gbp_block_scan
+// does.  The thread that scans entries 2t and 2t+1 also keeps their
+// cursors base0/base1 (where the next row of the bucket goes in `out`):
+// it publishes delta[b] = cursor - start for the tile's stores, then
+// moves the cursor past the tile's rows.  Ends with a barrier.
+__device__ __forceinline__ void gbp_tile_scan(uint32_t* lstart,
+                                              uint32_t* delta, uint32_t nb,
+                                              uint32_t* wtmp,
+                                              uint32_t* base0,
+                                              uint32_t* base1) {
+  const uint32_t i0 = 2 * threadIdx.x;
+  const uint32_t x0 = i0 < nb ? lstart[i0] : 0;
+  const uint32_t x1 = i0 + 1 < nb ? lstart[i0 + 1] : 0;
+  const uint32_t s = x0 + x1;
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  uint32_t run = s;  // inclusive wave scan
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(run, off);
+    if (lane >= off) run += up;
+  }
+  if (lane == 63) wtmp[w] = run;
+  __syncthreads();
+  uint32_t wbase = 0;
+  for (int w2 = 0; w2 < w; ++w2) wbase += wtmp[w2];
+  const uint32_t excl = wbase + run - s;
+  if (i0 < nb) {
+    lstart[i0] = excl;
+    delta[i0] = *base0 - excl;
+    *base0 += x0;
+  }
+  if (i0 + 1 < nb) {
+    lstart[i0 + 1] = excl + x0;
+    delta[i0 + 1] = *base1 - (excl + x0);
+    *base1 += x1;
+  }
+  __syncthreads();
+}
+
+#define GBP_SCATTER_R (GBP_SCATTER_ROWS / GBP_THREADS)
+
+// The tiles [t0, t1) of one group: k_gbp_scatter below.
+template <bool WIDE>
+__device__ __forceinline__ void gbp_scatter_group(
+    const int64_t* keys, const int64_t* vals, int64_t n, int64_t t0,
+    int64_t t1, uint32_t nb, uint32_t seed, uint32_t mask, uint32_t shift,
+    const uint32_t* grow, const uint32_t* totals, GbPair* out, GbPair* stage,
+    uint32_t* lstart, uint32_t* delta, uint32_t* wtmp) {
+  constexpr int R = GBP_SCATTER_R;
+  long long k[R], v[R], kn[R], vn[R];
+  uint32_t br[R];  // bucket << 16 | rank of the row inside its bucket
+  // The small loads go first: loads return in order, and the scan below
+  // should not wait for the tile's rows.
+  const uint32_t i0 = 2 * threadIdx.x;
+  const uint2 tot = i0 + 1 < nb ? *(const uint2*)(totals + i0)
+                                : make_uint2(0, 0);
+  const uint2 gs = i0 + 1 < nb ? *(const uint2*)(grow + i0)
+                               : make_uint2(0, 0);
+  gbp_load_rows<WIDE>(keys, t0 * GBP_SCATTER_ROWS, n, k);
+  gbp_load_rows<WIDE>(vals, t0 * GBP_SCATTER_ROWS, n, v);
+  if (i0 + 1 < nb) {  // nb is a power of two >= 2
+    lstart[i0] = 0;
+    lstart[i0 + 1] = 0;
+    delta[i0] = tot.x;
+    delta[i0 + 1] = tot.y;
+  }
+  __syncthreads();
+  gbp_block_scan(delta, nb, wtmp);  // start of each bucket in `out`
+  // cursors of buckets 2t and 2t+1: uint32 arithmetic wraps consistently
+  // (n < 2^31)
+  uint32_t base0 = i0 < nb ? delta[i0] + gs.x : 0;
+  uint32_t base1 = i0 + 1 < nb ? delta[i0 + 1] + gs.y : 0;
+  for (int64_t t = t0; t < t1; ++t) {
+    const uint32_t cnt = (uint32_t)min((int64_t)GBP_SCATTER_ROWS,
+                                       n - t * GBP_SCATTER_ROWS);
+    if (t + 1 < t1) {
+      gbp_load_rows<WIDE>(keys, (t + 1) * GBP_SCATTER_ROWS, n, kn);
+      gbp_load_rows<WIDE>(vals, (t + 1) * GBP_SCATTER_ROWS, n, vn);
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      if (gbp_row<WIDE>(j) < cnt) {
+        const uint32_t b = gbp_bucket(k[j], seed, mask, shift);
+        br[j] = (b << 16) | atomicAdd(&lstart[b], 1u);
+      }
+    }
+    __syncthreads();
+    gbp_tile_scan(lstart, delta, nb, wtmp, &base0, &base1);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      if (gbp_row<WIDE>(j) < cnt) {
+        GbPair pr;
+        pr.k = k[j];
+        pr.v = v[j];
+        stage[lstart[br[j] >> 16] + (br[j] & 0xffffu)] = pr;
+      }
+    }
+    __syncthreads();
+    // lstart is free from here: clear it for the next tile
+    for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) lstart[b] = 0;
+    // destination of staged position p of bucket b = delta[b] + p
+    for (uint32_t p = threadIdx.x; p < cnt; p += GBP_THREADS) {
+      const GbPair pr = stage[p];
+      const uint32_t b = gbp_bucket(pr.k, seed, mask, shift);
+      const uint32_t d = delta[b] + p;
+      if (d < n) out[d] = pr;  // always true; keeps a bad offset in bounds
+    }
+    if (t + 1 < t1) {
+      __syncthreads();  // stage, delta and lstart go to the next tile
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        k[j] = kn[j];
+        v[j] = vn[j];
+      }
+    }
+  }
+}
+
+// One workgroup per group of G consecutive tiles.  gsum holds the scanned
+// matrix (rows of each bucket in earlier groups), totals the rows per
+// bucket; together they give the group's cursor into each bucket's
+// segment, which then advances tile by tile without leaving the
+// workgroup.  The next tile's rows are loaded while the current tile
+// goes through LDS.  Consecutive groups are mapped to workgroups 8 apart
+// so neighbouring runs of a bucket are written through the same XCD's L2
+// and merge into whole lines there.
 extern "C" __global__ __launch_bounds__(GBP_THREADS) void k_gbp_scatter(
     const int64_t* keys, const int64_t* vals, int64_t n, int64_t ntiles,
-    uint32_t nb, uint32_t seed, uint32_t mask, uint32_t shift,
-    const uint32_t* hist, const uint32_t* totals, GbPair* out) {
+    uint32_t G, int64_t ngroups, uint32_t nb, uint32_t seed, uint32_t mask,
+    uint32_t shift, const uint32_t* gsum, const uint32_t* totals,
+    GbPair* out) {
   __shared__ GbPair stage[GBP_SCATTER_ROWS];
   __shared__ uint32_t lstart[GBP_MAX_BUCKETS];
   __shared__ uint32_t delta[GBP_MAX_BUCKETS];
   __shared__ uint32_t wtmp[GBP_THREADS / 64];
-  const int64_t per_xcd = (ntiles + 7) / 8;
-  const int64_t tile = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  if (tile >= ntiles) return;
-  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS) {
-    lstart[b] = 0;
-    delta[b] = totals[b];
-  }
-  __syncthreads();
-  constexpr int R = GBP_SCATTER_ROWS / GBP_THREADS;
-  const int64_t base = tile * GBP_SCATTER_ROWS;
-  const uint32_t cnt = (uint32_t)min((int64_t)GBP_SCATTER_ROWS, n - base);
-  long long k[R], v[R];
-  uint32_t br[R];  // bucket << 16 | rank of the row inside its bucket
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const uint32_t p = j * GBP_THREADS + threadIdx.x;
-    if (p < cnt) {
-      k[j] = keys[base + p];
-      v[j] = vals[base + p];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const uint32_t p = j * GBP_THREADS + threadIdx.x;
-    if (p < cnt) {
-      const uint32_t b = gbp_bucket(k[j], seed, mask, shift);
-      br[j] = (b << 16) | atomicAdd(&lstart[b], 1u);
-    }
-  }
-  __syncthreads();
-  gbp_block_scan(lstart, nb, wtmp);  // start of each bucket in the tile
-  gbp_block_scan(delta, nb, wtmp);   // start of each bucket in `out`
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const uint32_t p = j * GBP_THREADS + threadIdx.x;
-    if (p < cnt) {
-      GbPair pr;
-      pr.k = k[j];
-      pr.v = v[j];
-      stage[lstart[br[j] >> 16] + (br[j] & 0xffffu)] = pr;
-    }
-  }
-  // destination of staged position p of bucket b = delta[b] + p
-  // (uint32 arithmetic wraps consistently; n < 2^31)
-  const uint32_t* hrow = hist + tile * nb;
-  for (uint32_t b = threadIdx.x; b < nb; b += GBP_THREADS)
-    delta[b] += hrow[b] - lstart[b];
-  __syncthreads();
-  for (uint32_t p = threadIdx.x; p < cnt; p += GBP_THREADS) {
-    const GbPair pr = stage[p];
-    const uint32_t b = gbp_bucket(pr.k, seed, mask, shift);
-    const uint32_t d = delta[b] + p;
-    if (d < n) out[d] = pr;  // always true; keeps a bad offset in bounds
-  }
+  const int64_t per_xcd = (ngroups + 7) / 8;
+  const int64_t g = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  if (g >= ngroups) return;
+  int64_t t0, t1;
+  gbp_group_tiles(g, G, ntiles, &t0, &t1);
+  const uint32_t* grow = gsum + g * nb;
+  if ((((uintptr_t)keys | (uintptr_t)vals) & 15) == 0)
+    gbp_scatter_group<true>(keys, vals, n, t0, t1, nb, seed, mask, shift,
+                            grow, totals, out, stage, lstart, delta, wtmp);
+  else
+    gbp_scatter_group<false>(keys, vals, n, t0, t1, nb, seed, mask, shift,
+                             grow, totals, out, stage, lstart, delta, wtmp);
 }
 
 // One row through the tile's LDS table; false when the bounded probe

@@ -46,6 +46,8 @@ class Options:
     combine: str = "auto"       # BIGSLICE_GB_COMBINE: auto | hash | sort
     part: bool = True           # BIGSLICE_GB_PART: "part" in the chooser
     part_owned: bool = True     # BIGSLICE_GB_PART_OWNED: owned slices
+    part_group: int = 0         # BIGSLICE_GB_PART_GROUP: scatter tiles per
+                                # workgroup, 0 = the extension's rule
     lds_blocks: int = 4096      # BIGSLICE_GB_LDS_BLOCKS: grid cap, "lds"
     sample_rows: int = 1 << 19  # BIGSLICE_GB_SAMPLE_ROWS
     debug: bool = False         # BIGSLICE_GB_DEBUG: chooser trace
@@ -59,6 +61,7 @@ class Options:
             combine=env.get("BIGSLICE_GB_COMBINE", "auto"),
             part=env.get("BIGSLICE_GB_PART", "1") == "1",
             part_owned=env.get("BIGSLICE_GB_PART_OWNED", "1") == "1",
+            part_group=int(env.get("BIGSLICE_GB_PART_GROUP", "0")),
             lds_blocks=int(env.get("BIGSLICE_GB_LDS_BLOCKS", "4096")),
             sample_rows=int(env.get("BIGSLICE_GB_SAMPLE_ROWS",
                                     str(1 << 19))),
@@ -381,7 +384,8 @@ class GroupTable:
             kind, nbuckets = plan
             _C.groupby_insert_part(keys, vals[0], self.tkeys, self.tabs[0],
                                    self.flags, MAX_PROBES, nbuckets,
-                                   *([1] if kind == "owned" else []))
+                                   1 if kind == "owned" else 0,
+                                   self.opts.part_group)
         else:
             _C.groupby_insert(keys, list(vals), self.codes, self.tkeys,
                               self.tabs, self.flags, MAX_PROBES)

@@ -229,10 +229,13 @@ def main():
         t = kernels.GroupTable([torch.int64], ["sum"], dev)
         t._alloc(cap)
         C = kernels._C
-        pairs, _ = C.groupby_part_scatter(bk, bv, cap, B)
-        out.update(rows=n, cap=cap, buckets=B)
+        # scatter tiles per workgroup: PART_GROUP forces it, 0 = the rule
+        G = int(os.environ.get("PART_GROUP", "0"))
+        pairs, _ = C.groupby_part_scatter(bk, bv, cap, B, G)
+        out.update(rows=n, cap=cap, buckets=B,
+                   group_tiles=G or C.groupby_part_group_tiles(n))
         out["scatter_ms"] = timeit(
-            lambda: C.groupby_part_scatter(bk, bv, cap, B), args.iters)
+            lambda: C.groupby_part_scatter(bk, bv, cap, B, G), args.iters)
         out["aggregate_ms"] = timeit(
             lambda: C.groupby_part_aggregate(
                 pairs, t.tkeys, t.tabs[0], t.flags, kernels.MAX_PROBES),
@@ -240,7 +243,7 @@ def main():
         out["part_ms"] = timeit(
             lambda: C.groupby_insert_part(
                 bk, bv, t.tkeys, t.tabs[0], t.flags, kernels.MAX_PROBES,
-                B), args.iters)
+                B, 0, G), args.iters)
         out["plain_ms"] = timeit(
             lambda: C.groupby_insert(
                 bk, [bv], t.codes, t.tkeys, t.tabs, t.flags,
@@ -254,8 +257,9 @@ def main():
             Bo = own[0]
             out["owned_buckets"], out["owned_slice"] = own
             out["owned_scatter_ms"] = timeit(
-                lambda: C.groupby_part_scatter(bk, bv, cap, Bo), args.iters)
-            po, to = C.groupby_part_scatter(bk, bv, cap, Bo)
+                lambda: C.groupby_part_scatter(bk, bv, cap, Bo, G),
+                args.iters)
+            po, to = C.groupby_part_scatter(bk, bv, cap, Bo, G)
             # rows the owners leave to the cleanup pass: an upper bound
             # on the global atomics that remain.  Taken on the first run
             # (spilled rows overwrite consumed ones, so the buffer is
@@ -270,7 +274,7 @@ def main():
             out["owned_part_ms"] = timeit(
                 lambda: C.groupby_insert_part(
                     bk, bv, t.tkeys, t.tabs[0], t.flags,
-                    kernels.MAX_PROBES, Bo, 1), args.iters)
+                    kernels.MAX_PROBES, Bo, 1, G), args.iters)
         assert int(t.flags[1].item()) == 0, "table overflow"
         # global atomics of one aggregate pass = rows that missed the
         # LDS tables + flushed slots; counted on a fresh table as the
