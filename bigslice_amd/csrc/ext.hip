@@ -28,6 +28,8 @@
 #include "expr.hip"
 #include "tokenize.hip"
 #include "groupby_multi.hip"
+#include "iddict.hip"
+#include "bytes_gather.hip"
 
 namespace {
 
@@ -1485,6 +1487,151 @@ std::vector<torch::Tensor> tokenize_bytes(torch::Tensor data,
   return out;
 }
 
+// ------------------------------------------------- id dictionary (K23)
+
+// A caller-owned dictionary table: tags int64[cap+1] filled with the
+// sentinel, ref int64[cap+1], cap a power of two below 2^31.  Returns cap.
+int64_t idd_table(const torch::Tensor& tags, const torch::Tensor& ref) {
+  const int64_t cap = tags.size(0) - 1;
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && cap < (int64_t(1) << 31),
+              "capacity must be 2^k below 2^31");
+  for (const auto* t : {&tags, &ref})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 1 &&
+                    t->scalar_type() == torch::kInt64 &&
+                    t->size(0) == cap + 1,
+                "tags and ref must be contiguous int64[cap+1] device tensors");
+  return cap;
+}
+
+void idd_ids(const torch::Tensor& ids) {
+  TORCH_CHECK(ids.is_cuda() && ids.is_contiguous() && ids.dim() == 1 &&
+                  ids.scalar_type() == torch::kInt64,
+              "ids must be a contiguous int64 device tensor");
+}
+
+// Claim a slot for every id not yet in the table.  lens[i] is the byte
+// length of row i; counters is int64[3] = {new rows, new bytes, overflow},
+// zeroed by the caller.  Returns newrows int64[n]: its first counters[0]
+// entries are the rows whose strings the caller appends, in the order of
+// their positions base, base + 1, ...
+torch::Tensor iddict_claim(torch::Tensor ids, torch::Tensor lens,
+                           torch::Tensor tags, torch::Tensor ref,
+                           int64_t base, torch::Tensor counters,
+                           int64_t max_probes) {
+  idd_ids(ids);
+  const int64_t n = ids.size(0);
+  const int64_t cap = idd_table(tags, ref);
+  TORCH_CHECK(lens.is_cuda() && lens.is_contiguous() && lens.dim() == 1 &&
+                  lens.scalar_type() == torch::kInt64 && lens.size(0) == n,
+              "lens must be a contiguous int64 device tensor, one per id");
+  TORCH_CHECK(counters.is_cuda() && counters.is_contiguous() &&
+                  counters.scalar_type() == torch::kInt64 &&
+                  counters.numel() >= 3,
+              "counters must be int64[3]");
+  TORCH_CHECK(max_probes >= 1 && base >= 0);
+  auto newrows = torch::empty({n}, ids.options());
+  if (n == 0) return newrows;
+  hipLaunchKernelGGL(k_idd_claim, dim3(gbm_blocks(n)), dim3(THREADS), 0,
+                     current_stream(), ids.data_ptr<int64_t>(), n,
+                     lens.data_ptr<int64_t>(), tags.data_ptr<int64_t>(),
+                     ref.data_ptr<int64_t>(), cap, base,
+                     newrows.data_ptr<int64_t>(),
+                     (unsigned long long*)counters.data_ptr<int64_t>(),
+                     max_probes);
+  HIP_CHECK(hipGetLastError());
+  return newrows;
+}
+
+// The position of every id, -1 when absent.
+torch::Tensor iddict_lookup(torch::Tensor ids, torch::Tensor tags,
+                            torch::Tensor ref, int64_t max_probes) {
+  idd_ids(ids);
+  const int64_t n = ids.size(0);
+  const int64_t cap = idd_table(tags, ref);
+  TORCH_CHECK(max_probes >= 1);
+  auto out = torch::empty({n}, ids.options());
+  if (n == 0) return out;
+  hipLaunchKernelGGL(k_idd_lookup, dim3(gbm_blocks(n)), dim3(THREADS), 0,
+                     current_stream(), ids.data_ptr<int64_t>(), n,
+                     tags.data_ptr<int64_t>(), ref.data_ptr<int64_t>(), cap,
+                     out.data_ptr<int64_t>(), max_probes);
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+// Move every entry of the old table into the new, empty one; overflow
+// (int32[1], zeroed by the caller) is raised when a probe chain of the
+// new table reaches max_probes.
+void iddict_rehash(torch::Tensor old_tags, torch::Tensor old_ref,
+                   torch::Tensor new_tags, torch::Tensor new_ref,
+                   torch::Tensor overflow, int64_t max_probes) {
+  const int64_t old_cap = idd_table(old_tags, old_ref);
+  const int64_t new_cap = idd_table(new_tags, new_ref);
+  TORCH_CHECK(overflow.is_cuda() && overflow.is_contiguous() &&
+                  overflow.scalar_type() == torch::kInt32 &&
+                  overflow.numel() >= 1,
+              "overflow must be int32[1]");
+  TORCH_CHECK(max_probes >= 1);
+  hipLaunchKernelGGL(k_idd_rehash, dim3(gbm_blocks(old_cap)), dim3(THREADS),
+                     0, current_stream(), old_tags.data_ptr<int64_t>(),
+                     old_ref.data_ptr<int64_t>(), old_cap,
+                     new_tags.data_ptr<int64_t>(),
+                     new_ref.data_ptr<int64_t>(), new_cap,
+                     overflow.data_ptr<int32_t>(), max_probes);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------ varlen row gather (K23)
+
+// Rows `rows` of the BYTES column (data, offsets) as a new zero-based
+// column (out_data, out_offsets).  offsets is absolute into data and may
+// be a slice (offsets[0] != 0).  total is the byte count of the result
+// when the caller knows it; -1 reads it back (the one host readback).
+std::vector<torch::Tensor> bytes_gather(torch::Tensor data,
+                                        torch::Tensor offsets,
+                                        torch::Tensor rows, int64_t total) {
+  TORCH_CHECK(data.is_cuda() && data.is_contiguous() && data.dim() == 1 &&
+                  data.scalar_type() == torch::kUInt8,
+              "bytes_gather: contiguous uint8 device data required");
+  TORCH_CHECK(offsets.is_cuda() && offsets.is_contiguous() &&
+                  offsets.dim() == 1 && offsets.size(0) >= 1 &&
+                  offsets.scalar_type() == torch::kInt64,
+              "bytes_gather: contiguous int64 device offsets required");
+  TORCH_CHECK(rows.is_cuda() && rows.dim() == 1 &&
+                  rows.scalar_type() == torch::kInt64,
+              "bytes_gather: int64 device row indices required");
+  rows = rows.contiguous();
+  const int64_t n = offsets.size(0) - 1;
+  const int64_t m = rows.size(0);
+  auto out_offsets = torch::zeros({m + 1}, offsets.options());
+  if (m == 0 || total == 0)
+    return {torch::empty({0}, data.options()), out_offsets};
+  auto stream = current_stream();
+  auto lens = torch::empty({m}, offsets.options());
+  hipLaunchKernelGGL(k_bg_lens, dim3(gbm_blocks(m)), dim3(THREADS), 0,
+                     stream, offsets.data_ptr<int64_t>(), n,
+                     rows.data_ptr<int64_t>(), m, lens.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  // 1-D: an outer-dim scan is several times slower (see tokenize_bytes)
+  auto incl = out_offsets.narrow(0, 1, m);
+  at::cumsum_out(incl, lens, 0);
+  if (total < 0) total = out_offsets[m].item<int64_t>();
+  if (total == 0) return {torch::empty({0}, data.options()), out_offsets};
+  auto out_data = torch::empty({total}, data.options());
+  TORCH_CHECK(((uintptr_t)out_data.data_ptr<uint8_t>() & 15) == 0,
+              "bytes_gather: output must be 16-byte aligned");
+  const int64_t ntiles = (total + BG_TILE - 1) / BG_TILE;
+  TORCH_CHECK(ntiles < (int64_t(1) << 31), "bytes_gather: result too large");
+  hipLaunchKernelGGL(k_bg_copy, dim3((uint32_t)ntiles), dim3(BG_BLOCK), 0,
+                     stream, data.data_ptr<uint8_t>(), data.size(0),
+                     offsets.data_ptr<int64_t>(), n,
+                     rows.data_ptr<int64_t>(), m,
+                     out_offsets.data_ptr<int64_t>(), total,
+                     out_data.data_ptr<uint8_t>());
+  HIP_CHECK(hipGetLastError());
+  return {out_data, out_offsets};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1566,4 +1713,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tokenize_bytes", &tokenize_bytes,
         "split BYTES rows into tokens on a delimiter set (K20)");
   m.attr("TOKENIZE_TILE_BYTES") = (int64_t)TOK_TILE;
+  m.def("iddict_claim", &iddict_claim,
+        "id dictionary: claim slots for new ids; returns the new rows (K23)");
+  m.def("iddict_lookup", &iddict_lookup,
+        "id dictionary: position of every id, -1 when absent (K23)");
+  m.def("iddict_rehash", &iddict_rehash,
+        "id dictionary: move a table into a larger one (K23)");
+  m.def("bytes_gather", &bytes_gather,
+        "variable-length row gather of a BYTES column (K23)",
+        py::arg("data"), py::arg("offsets"), py::arg("rows"),
+        py::arg("total") = -1);
+  m.attr("BYTES_GATHER_TILE_BYTES") = (int64_t)BG_TILE;
 }

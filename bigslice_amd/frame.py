@@ -165,6 +165,21 @@ class BytesColumn:
         src = self.offsets[idx][row_id] + within
         return BytesColumn(self.data[src], offs)
 
+    def gather(self, indices: torch.Tensor,
+               total: int = None) -> "BytesColumn":
+        """select(indices) in one HIP copy kernel (csrc/bytes_gather.hip)
+        for a device column; works on a zero-copy slice as it is.  total
+        is the byte count of the result when the caller knows it, which
+        saves the one host readback.  A host column calls select."""
+        from . import kernels
+        if not self.data.is_cuda or (not kernels.have_extension()
+                                     and kernels.ALLOW_FALLBACK):
+            return self.select(indices)
+        from .kernels import iddict
+        data, offs = iddict.bytes_gather(
+            self.data, self.offsets, indices.to(self.offsets.device), total)
+        return BytesColumn(data, offs)
+
     def to(self, device, non_blocking=False) -> "BytesColumn":
         c = self.compacted()
         return BytesColumn(

@@ -203,7 +203,11 @@ def hash_columns(cols: Sequence, seed: int = 0) -> torch.Tensor:
             h = kernels.hash_columns_device(tensors, seed)
         for b in bytes_cols:
             hb = b.hash32(seed)
-            h = hb if h is None else (h ^ hb)
+            if h is None:
+                h = hb
+            else:
+                # torch has no uint32 xor on the device: same bits as int32
+                h = (h.view(torch.int32) ^ hb.view(torch.int32)).view(h.dtype)
         return h
     h = None
     for c in cols:

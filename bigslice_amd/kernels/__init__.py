@@ -100,6 +100,10 @@ from .groupby import (  # noqa: E402,F401
 
 from .groupby_multi import MultiKeyTable, fingerprint64  # noqa: E402,F401
 
+# -- id dictionary and varlen row gather for BYTES key columns (K23) -------
+
+from .iddict import IdDictionary, bytes_gather  # noqa: E402,F401
+
 
 # -- sort (K6) -------------------------------------------------------------
 

@@ -12,6 +12,10 @@ row-wise open-addressing table with whole-batch device aggregation:
 * 2..8 int64/int32 key columns + numeric values: a HIP table keyed by the
   whole tuple (csrc/groupby_multi.hip); other numeric composite keys and
   the CPU path use a lexicographic sort + segment reduce.
+* 2..8 key columns of which some are BYTES and the rest int64/int32, on a
+  GPU: the same table over the strings' 64-bit ids, with a HIP id
+  dictionary per BYTES column (csrc/iddict.hip) that keeps one exemplar
+  string per id for the output.
 * arbitrary keys/values/fns: a host dict accumulator (the reference's
   accum.go path).
 
@@ -22,6 +26,7 @@ device, arbitrary callables run on host.
 from __future__ import annotations
 
 import operator
+import os
 from typing import Callable, List, Optional, Sequence, Union
 
 import torch
@@ -82,8 +87,10 @@ def make_aggregator(schema: Schema, agg: Aggregation, device: str,
                     seed: int = config.COMBINER_HASH_SEED):
     """Choose the right aggregator implementation for a schema:
     tensor path for any all-numeric schema (single- or multi-column
-    keys), device dictionary path for a single BYTES key, host dict
-    path for object keys / arbitrary combine fns."""
+    keys), device dictionary path for a single BYTES key, id-tuple path
+    for a composite key with BYTES columns on a GPU
+    (BIGSLICE_GB_BYTES_MULTIKEY=0 turns that off), host dict path for
+    object keys / arbitrary combine fns."""
     from ..schema import is_bytes
     numeric = (not any(is_object(d) or is_bytes(d)
                        for d in schema.dtypes))
@@ -94,7 +101,116 @@ def make_aggregator(schema: Schema, agg: Aggregation, device: str,
             and not any(is_object(d) or is_bytes(d)
                         for d in schema.dtypes[1:])):
         return BytesKeyAggregator(schema, agg, device)
+    if device.startswith("cuda") and bytes_tuple_supported(schema, agg) \
+            and os.environ.get("BIGSLICE_GB_BYTES_MULTIKEY", "1") != "0":
+        from .. import kernels
+        if kernels.have_extension():
+            return BytesTupleAggregator(schema, agg, device)
+        if not kernels.ALLOW_FALLBACK:
+            kernels._require("groupby")  # no silent eager fallback
     return DictAggregator(schema, agg)
+
+
+def bytes_tuple_supported(schema: Schema, agg: Aggregation) -> bool:
+    """Shapes BytesTupleAggregator takes: builtin aggregations, a prefix
+    of 2..MAX_KEY_COLS columns of which at least one is BYTES and the
+    others int64/int32, and dense value columns MultiKeyTable accepts
+    (with every BYTES key counted as its int64 id)."""
+    from ..kernels import groupby_multi as gbm
+    from ..schema import is_bytes
+    keys = schema.dtypes[:schema.prefix]
+    vals = schema.dtypes[schema.prefix:]
+    if not agg.all_builtin or not any(is_bytes(d) for d in keys):
+        return False
+    if any(is_object(d) or is_bytes(d) for d in vals):
+        return False
+    if any(is_object(d) for d in keys):
+        return False
+    return gbm.multikey_supported(
+        [torch.int64 if is_bytes(d) else d for d in keys], vals, agg.aggs)
+
+
+class BytesTupleAggregator:
+    """Keyed reduce over a composite key with BYTES columns (K23): 2 to
+    MAX_KEY_COLS key columns, at least one BYTES, the others int64/int32.
+
+    Every BYTES key column is replaced by its 64-bit id and the id tuples
+    group through the numeric TensorAggregator (the HIP MultiKeyTable on
+    a GPU, whose collision fallback is _combine_once over the id tuples).
+    One IdDictionary per BYTES column (a device hash table; no sort, no
+    torch.unique) keeps one exemplar string per id for the output.
+    Grouping is by id: exact up to the 2^-64-per-pair id collision that
+    BytesColumn documents.
+
+    On "cpu" the dictionary runs its host mirror and the inner aggregator
+    its sort path; no session routes here on the CPU, it is how the logic
+    is tested without a GPU.
+    """
+
+    # small frames are concatenated before either table is touched, as
+    # in TensorAggregator: one set of launches instead of many
+    _SMALL_ROWS = 1 << 20
+
+    def __init__(self, schema: Schema, agg: Aggregation, device: str):
+        from ..kernels.iddict import IdDictionary
+        from ..schema import Schema as S
+        from ..schema import is_bytes
+        if not bytes_tuple_supported(schema, agg):
+            raise ValueError("unsupported composite BYTES key shape")
+        self.schema = schema
+        self.nkey = schema.prefix
+        self.device = device
+        self.bytes_cols = [i for i in range(self.nkey)
+                           if is_bytes(schema.dtypes[i])]
+        inner_dts = tuple(torch.int64 if i in self.bytes_cols else dt
+                          for i, dt in enumerate(schema.dtypes))
+        self.inner = TensorAggregator(S(inner_dts, self.nkey), agg, device)
+        self.dicts = {i: IdDictionary(device) for i in self.bytes_cols}
+        self._pending: List[Frame] = []
+        self._pending_rows = 0
+
+    def add(self, frame: Frame) -> None:
+        if len(frame) == 0:
+            return
+        if frame.device != self.device:
+            frame = frame.to(self.device)
+        if len(frame) < self._SMALL_ROWS:
+            self._pending.append(frame)
+            self._pending_rows += len(frame)
+            if self._pending_rows >= 4 * self._SMALL_ROWS:
+                self._flush_pending()
+            return
+        self._insert(frame)
+
+    def _flush_pending(self) -> None:
+        if not self._pending:
+            return
+        f = Frame.concat(self._pending)
+        self._pending.clear()
+        self._pending_rows = 0
+        self._insert(f)
+
+    def _insert(self, f: Frame) -> None:
+        cols = list(f.columns)
+        for i in self.bytes_cols:
+            ids = cols[i].ids64()
+            self.dicts[i].add(ids, cols[i])
+            cols[i] = ids
+        self.inner.add(Frame(cols, self.nkey))
+
+    def result_frames(self, chunk: int):
+        self._flush_pending()
+        first = True
+        for f in self.inner.result_frames(chunk):
+            if first:
+                from ..utils import stats
+                stats.DEFAULT.add("combiner/bytes_tuple_tables", 1)
+                first = False
+            cols = list(f.columns)
+            for i in self.bytes_cols:
+                d = self.dicts[i]
+                cols[i] = d.strings().gather(d.lookup(cols[i]))
+            yield Frame(cols, self.nkey, combined_id=f.combined_id)
 
 
 class BytesKeyAggregator:

@@ -115,6 +115,41 @@ def device_wordcount(nshard: int, open_fn: Callable[[], Iterable[str]]
     return Reduce(pairs, "sum")
 
 
+# -- device_term_counts: per-document word counts on device ----------------
+
+def device_term_counts(nshard: int, open_fn: Callable[[], Iterable[str]]
+                       ) -> Slice:
+    """Slice<word: bytes, doc: int, count: int>: how often every word
+    occurs in every document, the step after wordcount.  Each line of
+    open_fn is tagged with its document number, "<doc>\\t<text>" (a
+    document may span any number of lines).  ScanReader -> Map (text,
+    doc) -> Tokenize, which repeats doc per word -> Map (word, doc, 1)
+    -> Reduce("sum") over the composite key (word, doc): on a GPU
+    session that Reduce groups by (id of word, doc) in the device table
+    (K23, ops.aggregate.BytesTupleAggregator).  Words split on ASCII
+    whitespace; exact up to the 2^-64 dictionary-id collision
+    BytesColumn documents.  Build inside a bigslice_amd.func."""
+    import torch
+
+    from .ops import Tokenize
+
+    def untag(lines):
+        docs, texts = [], []
+        for line in lines:
+            doc, _, text = line.partition("\t")
+            docs.append(int(doc))
+            texts.append(text)
+        return texts, torch.tensor(docs, dtype=torch.int64)
+
+    tagged = Map(ScanReader(nshard, open_fn), untag, out_schema=(object, int))
+    toks = Tokenize(tagged, col=0, prefix=2)
+    triples = Map(toks,
+                  lambda w, d: (w, d, torch.ones(len(w), dtype=torch.int64,
+                                                 device=d.device)),
+                  out_schema=(bytes, int, int), prefix=2)
+    return Reduce(triples, "sum")
+
+
 # -- gpu_wordcount: device dictionary ids via K17 ------------------------
 
 _GPU_WC_RUNS = {}

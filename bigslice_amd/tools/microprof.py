@@ -6,6 +6,8 @@
   python -m bigslice_amd.tools.microprof tokenize --iters 20
   python -m bigslice_amd.tools.microprof groupby_multi --rows 8388608
   python -m bigslice_amd.tools.microprof runs_multi --rows 8388608
+  python -m bigslice_amd.tools.microprof iddict --rows 8388608
+  python -m bigslice_amd.tools.microprof bytes_gather
 
 Times each kernel phase with hipEvents over --iters iterations.  Keep
 runs short: this is the target for `rocprofv3 --pmc ... -- ...`.
@@ -174,13 +176,108 @@ def runs_multi(dev, g, iters, rows, nkeys, ncols):
     return out
 
 
+def _hex_words(idx):
+    """Row i is the 8 hex digits of idx[i], lowest first: distinct
+    numbers give distinct 8-byte strings."""
+    from bigslice_amd.frame import BytesColumn
+    digits = torch.tensor(list(b"0123456789abcdef"), dtype=torch.uint8,
+                          device=idx.device)
+    shifts = torch.arange(0, 32, 4, device=idx.device)
+    data = digits[(idx[:, None] >> shifts) & 15].flatten()
+    offsets = torch.arange(idx.shape[0] + 1, dtype=torch.int64,
+                           device=idx.device) * 8
+    return BytesColumn(data, offsets)
+
+
+def iddict(dev, g, iters, rows, nkeys, cap):
+    """The id dictionary (K23) over one batch of `rows` 8-byte strings
+    from `nkeys` distinct ones, into a presized table.  Warm (every id
+    present after the warmups: pure probe, as claim_ms of groupby_multi):
+    the claim, the lookup and a whole add with its one readback.  Fresh:
+    a whole add into an empty presized dictionary, the gather of the
+    exemplars included."""
+    C = kernels._C
+    col = _hex_words(torch.randint(0, nkeys, (rows,), dtype=torch.int64,
+                                   device=dev, generator=g))
+    ids = col.ids64()
+    lens = col.lengths().contiguous()
+    cap = cap or kernels._next_pow2(4 * nkeys)
+    d = kernels.IdDictionary(dev, cap_hint=cap)
+    d.add(ids, col)
+    assert d.regrows == 0 and d.cap == cap, (d.regrows, d.cap)
+    out = {"which": "iddict", "rows": rows, "nkeys": nkeys, "cap": d.cap,
+           "distinct": len(d)}
+    pos = d.lookup(ids)
+    assert int(pos.min()) >= 0
+    k = min(rows, 1 << 20)
+    back = d.strings().gather(pos[:k])
+    assert torch.equal(back.data, col.data[:8 * k])
+    del pos, back
+    counters = torch.zeros(3, dtype=torch.int64, device=dev)
+    out["claim_ms"] = timeit(
+        lambda: C.iddict_claim(ids, lens, d.tags, d.ref, len(d), counters,
+                               kernels.MAX_PROBES), iters)
+    assert counters.tolist() == [0, 0, 0], counters.tolist()
+    out["lookup_ms"] = timeit(
+        lambda: C.iddict_lookup(ids, d.tags, d.ref, kernels.MAX_PROBES),
+        iters)
+    out["add_warm_ms"] = timeit(lambda: d.add(ids, col), iters)
+    # a readback on an idle stream: what the add's one readback costs
+    # beyond waiting for the claim
+    out["readback_ms"] = timeit(
+        lambda: torch.zeros(3, dtype=torch.int64, device=dev).tolist(),
+        iters)
+    out["readback_share_of_add"] = out["readback_ms"] / out["add_warm_ms"]
+
+    def fresh():
+        f = kernels.IdDictionary(dev, cap_hint=cap)
+        f.add(ids, col)
+    out["add_fresh_ms"] = timeit(fresh, iters)
+    out["claim_grows_per_s"] = rows / out["claim_ms"] / 1e6
+    out["lookup_grows_per_s"] = rows / out["lookup_ms"] / 1e6
+    return out
+
+
+def bytes_gather_ab(dev, g, iters, rows=1 << 20):
+    """BytesColumn.gather (K23, csrc/bytes_gather.hip) against
+    BytesColumn.select on the same random indices: `rows` rows of 4..12
+    bytes and `rows` rows of 64 bytes, one readback each included."""
+    from bigslice_amd.frame import BytesColumn
+    out = {"which": "bytes_gather", "rows": rows}
+    for tag, lo, hi in (("short", 4, 12), ("long", 64, 64)):
+        lens = torch.randint(lo, hi + 1, (rows,), dtype=torch.int64,
+                             device=dev, generator=g)
+        offsets = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens, 0, out=offsets[1:])
+        total = int(offsets[-1])
+        col = BytesColumn(torch.randint(0, 256, (total,), dtype=torch.uint8,
+                                        device=dev, generator=g), offsets)
+        idx = torch.randint(0, rows, (rows,), dtype=torch.int64, device=dev,
+                            generator=g)
+        want, got = col.select(idx), col.gather(idx)
+        assert torch.equal(want.data, got.data)
+        assert torch.equal(want.offsets, got.offsets)
+        nbytes = int(want.data.shape[0])
+        del want, got
+        s_ms = timeit(lambda: col.select(idx), iters)
+        g_ms = timeit(lambda: col.gather(idx), iters)
+        k_ms = timeit(lambda: col.gather(idx, total=nbytes), iters)
+        out[tag] = {"bytes": nbytes, "select_ms": s_ms, "gather_ms": g_ms,
+                    "gather_known_total_ms": k_ms,
+                    "select_gbps": nbytes / s_ms / 1e6,
+                    "gather_gbps": nbytes / g_ms / 1e6,
+                    "gather_known_total_gbps": nbytes / k_ms / 1e6}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", choices=["groupby", "groupby_part", "insert",
                                       "groupby_multi", "runs_multi",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
-                                      "runs", "tokenize"])
+                                      "runs", "tokenize", "iddict",
+                                      "bytes_gather"])
     ap.add_argument("--cap", type=int, default=0,
                     help="table capacity (0 = 2x nkeys rounded up)")
     ap.add_argument("--rows", type=int, default=125_000_000)
@@ -196,6 +293,13 @@ def main():
     g.manual_seed(1)
     if args.which == "tokenize":
         print(json.dumps(tokenize_ab(dev, g, args.iters)))
+        return
+    if args.which == "iddict":
+        print(json.dumps(iddict(dev, g, args.iters, args.rows, args.nkeys,
+                                args.cap)))
+        return
+    if args.which == "bytes_gather":
+        print(json.dumps(bytes_gather_ab(dev, g, args.iters)))
         return
     if args.which == "groupby_multi":
         print(json.dumps(groupby_multi(dev, g, args.iters, args.rows,
