@@ -74,6 +74,52 @@ hipStream_t current_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
+// Blocks of a grid-stride launch over n rows, `threads` rows per block.
+int grid_blocks(int64_t n, int threads = THREADS) {
+  return (int)std::min<int64_t>((n + threads - 1) / threads, 32768);
+}
+
+// Launch a kernel templated on the number of key columns at the
+// instantiation for nk columns: 2, 3 and 4 have their own, the rest take
+// the generic one, <0>.
+#define LAUNCH_NK(kernel, nk, blocks, threads, ...)                       \
+  do {                                                                    \
+    switch (nk) {                                                         \
+      case 2:                                                             \
+        hipLaunchKernelGGL(kernel<2>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+        break;                                                            \
+      case 3:                                                             \
+        hipLaunchKernelGGL(kernel<3>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+        break;                                                            \
+      case 4:                                                             \
+        hipLaunchKernelGGL(kernel<4>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+        break;                                                            \
+      default:                                                            \
+        hipLaunchKernelGGL(kernel<0>, dim3(blocks), dim3(threads), 0,     \
+                           current_stream(), __VA_ARGS__);                \
+    }                                                                     \
+    HIP_CHECK(hipGetLastError());                                         \
+  } while (0)
+
+// lo..hi contiguous int64 device columns of one length on one device,
+// `what` in the message; returns the length.
+int64_t int64_cols(const std::vector<torch::Tensor>& cols, int lo, int hi,
+                   const char* what) {
+  TORCH_CHECK((int)cols.size() >= lo && (int)cols.size() <= hi, what, ": ",
+              lo, "..", hi, " columns supported");
+  const int64_t n = cols[0].size(0);
+  for (const auto& c : cols)
+    TORCH_CHECK(c.is_cuda() && c.is_contiguous() &&
+                    c.scalar_type() == torch::kInt64 && c.dim() == 1 &&
+                    c.size(0) == n && c.device() == cols[0].device(),
+                what, " must be contiguous int64 device tensors of one "
+                "length");
+  return n;
+}
+
 constexpr int32_t MAX_LDS_PARTS = 4096;
 
 // Rows per block for the partition kernels: target ~4096 workgroups so
@@ -276,7 +322,7 @@ void groupby_insert(torch::Tensor keys, std::vector<torch::Tensor> vals,
   if (n == 0) return;
   int64_t cap = table_cap(tkeys, tabs, flags);
   ValCols vc = make_val_cols(vals, tabs, aggs);
-  int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
+  int blocks = grid_blocks(n);
   hipLaunchKernelGGL(k_groupby_insert, dim3(blocks), dim3(THREADS), 0,
                      current_stream(), keys.data_ptr<int64_t>(), n, vc,
                      tkeys.data_ptr<int64_t>(), cap, GB_HASH_SEED,
@@ -291,7 +337,7 @@ torch::Tensor slot_pids(torch::Tensor keys, int64_t cap,
   keys = keys.contiguous();
   int64_t n = keys.size(0);
   auto pids = torch::empty({n}, keys.options().dtype(torch::kInt32));
-  int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
+  int blocks = grid_blocks(n);
   hipLaunchKernelGGL(k_slot_pids, dim3(blocks), dim3(THREADS), 0,
                      current_stream(), keys.data_ptr<int64_t>(), n, cap,
                      (int32_t)nparts, GB_HASH_SEED,
@@ -558,30 +604,6 @@ std::vector<torch::Tensor> groupby_compact(torch::Tensor tkeys,
 
 // ------------------------------------------- multi-column group-by (K21)
 
-// Launch one of the k_gbm_* kernels at the instantiation for nk key
-// columns: 2, 3 and 4 have their own, the rest take the generic one.
-#define GBM_LAUNCH(kernel, nk, blocks, ...)                              \
-  do {                                                                   \
-    switch (nk) {                                                        \
-      case 2:                                                            \
-        hipLaunchKernelGGL(kernel<2>, dim3(blocks), dim3(THREADS), 0,    \
-                           current_stream(), __VA_ARGS__);               \
-        break;                                                           \
-      case 3:                                                            \
-        hipLaunchKernelGGL(kernel<3>, dim3(blocks), dim3(THREADS), 0,    \
-                           current_stream(), __VA_ARGS__);               \
-        break;                                                           \
-      case 4:                                                            \
-        hipLaunchKernelGGL(kernel<4>, dim3(blocks), dim3(THREADS), 0,    \
-                           current_stream(), __VA_ARGS__);               \
-        break;                                                           \
-      default:                                                           \
-        hipLaunchKernelGGL(kernel<0>, dim3(blocks), dim3(THREADS), 0,    \
-                           current_stream(), __VA_ARGS__);               \
-    }                                                                    \
-    HIP_CHECK(hipGetLastError());                                        \
-  } while (0)
-
 uint64_t gbm_fp_mask(int64_t fp_bits) {
   TORCH_CHECK(fp_bits >= 1 && fp_bits <= 64, "fp_bits must be in [1, 64]");
   return fp_bits == 64 ? ~uint64_t(0) : (uint64_t(1) << fp_bits) - 1;
@@ -590,16 +612,9 @@ uint64_t gbm_fp_mask(int64_t fp_bits) {
 // The batch side of MkCols: 2..MAX_KEY_COLS contiguous int64 device
 // columns of one length, which is returned.
 int64_t gbm_batch_keys(MkCols& kc, const std::vector<torch::Tensor>& keys) {
-  TORCH_CHECK(keys.size() >= 2 && (int)keys.size() <= MAX_KEY_COLS,
-              "2..", MAX_KEY_COLS, " key columns supported");
+  const int64_t n = int64_cols(keys, 2, MAX_KEY_COLS, "key columns");
   kc.n = (int)keys.size();
-  const int64_t n = keys[0].size(0);
   for (size_t c = 0; c < keys.size(); ++c) {
-    TORCH_CHECK(keys[c].is_cuda() && keys[c].is_contiguous() &&
-                    keys[c].scalar_type() == torch::kInt64 &&
-                    keys[c].dim() == 1 && keys[c].size(0) == n,
-                "key columns must be contiguous int64 device tensors of "
-                "one length");
     kc.src[c] = keys[c].data_ptr<int64_t>();
     kc.tab[c] = nullptr;
   }
@@ -627,10 +642,6 @@ int64_t gbm_table(MkCols& kc, const torch::Tensor& tags,
   return cap;
 }
 
-int gbm_blocks(int64_t n) {
-  return (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
-}
-
 // The device tag of every row (tests compare it with the torch mirror,
 // kernels/groupby_multi.fingerprint64).
 torch::Tensor groupby_mk_fingerprint(std::vector<torch::Tensor> keys,
@@ -640,8 +651,8 @@ torch::Tensor groupby_mk_fingerprint(std::vector<torch::Tensor> keys,
   const uint64_t fp_mask = gbm_fp_mask(fp_bits);
   auto out = torch::empty({n}, keys[0].options());
   if (n == 0) return out;
-  GBM_LAUNCH(k_gbm_fingerprint, kc.n, gbm_blocks(n), kc, n, GB_HASH_SEED,
-             fp_mask, out.data_ptr<int64_t>());
+  LAUNCH_NK(k_gbm_fingerprint, kc.n, grid_blocks(n), THREADS, kc, n,
+            GB_HASH_SEED, fp_mask, out.data_ptr<int64_t>());
   return out;
 }
 
@@ -659,10 +670,10 @@ torch::Tensor groupby_mk_claim(std::vector<torch::Tensor> keys,
   TORCH_CHECK(max_probes >= 1);
   auto slots = torch::empty({n}, keys[0].options().dtype(torch::kInt32));
   if (n == 0) return slots;
-  GBM_LAUNCH(k_gbm_claim, kc.n, gbm_blocks(n), kc, n,
-             tags.data_ptr<int64_t>(), cap, GB_HASH_SEED, fp_mask,
-             (uint32_t*)slots.data_ptr<int32_t>(),
-             flags.data_ptr<int32_t>() + 1, max_probes);
+  LAUNCH_NK(k_gbm_claim, kc.n, grid_blocks(n), THREADS, kc, n,
+            tags.data_ptr<int64_t>(), cap, GB_HASH_SEED, fp_mask,
+            (uint32_t*)slots.data_ptr<int32_t>(),
+            flags.data_ptr<int32_t>() + 1, max_probes);
   return slots;
 }
 
@@ -687,9 +698,9 @@ void groupby_mk_accum(std::vector<torch::Tensor> keys,
     TORCH_CHECK(v.dim() == 1 && v.size(0) == n,
                 "value columns must have one entry per row");
   if (n == 0) return;
-  GBM_LAUNCH(k_gbm_accum, kc.n, gbm_blocks(n), kc, n, vc,
-             (const uint32_t*)slots.data_ptr<int32_t>(), cap,
-             flags.data_ptr<int32_t>() + 2);
+  LAUNCH_NK(k_gbm_accum, kc.n, grid_blocks(n), THREADS, kc, n, vc,
+            (const uint32_t*)slots.data_ptr<int32_t>(), cap,
+            flags.data_ptr<int32_t>() + 2);
 }
 
 // Streaming insert of one batch: both launches on the current stream.
@@ -1122,52 +1133,14 @@ std::vector<torch::Tensor> runs_sorted(torch::Tensor keys) {
 
 // ------------------------------ multi-column sorted-key primitives (K22)
 
-// Launch one of the runs_multi.hip kernels at the instantiation for nk
-// key columns: 2, 3 and 4 have their own, the rest take the generic one.
-#define MRUNS_LAUNCH(kernel, nk, blocks, threads, ...)                    \
-  do {                                                                    \
-    switch (nk) {                                                         \
-      case 2:                                                             \
-        hipLaunchKernelGGL(kernel<2>, dim3(blocks), dim3(threads), 0,     \
-                           current_stream(), __VA_ARGS__);                \
-        break;                                                            \
-      case 3:                                                             \
-        hipLaunchKernelGGL(kernel<3>, dim3(blocks), dim3(threads), 0,     \
-                           current_stream(), __VA_ARGS__);                \
-        break;                                                            \
-      case 4:                                                             \
-        hipLaunchKernelGGL(kernel<4>, dim3(blocks), dim3(threads), 0,     \
-                           current_stream(), __VA_ARGS__);                \
-        break;                                                            \
-      default:                                                            \
-        hipLaunchKernelGGL(kernel<0>, dim3(blocks), dim3(threads), 0,     \
-                           current_stream(), __VA_ARGS__);                \
-    }                                                                     \
-    HIP_CHECK(hipGetLastError());                                         \
-  } while (0)
-
-// 1..MAX_KEY_COLS contiguous int64 device columns of one length on one
-// device; returns the length.
-int64_t lex_cols(const std::vector<torch::Tensor>& cols, const char* what) {
-  TORCH_CHECK(!cols.empty() && (int)cols.size() <= MAX_KEY_COLS, what,
-              ": 1..", MAX_KEY_COLS, " key columns supported");
-  const int64_t n = cols[0].size(0);
-  for (const auto& c : cols)
-    TORCH_CHECK(c.is_cuda() && c.is_contiguous() &&
-                    c.scalar_type() == torch::kInt64 && c.dim() == 1 &&
-                    c.size(0) == n && c.device() == cols[0].device(),
-                what, ": key columns must be contiguous int64 device "
-                "tensors of one length");
-  return n;
-}
-
 // (distinct tuples per column, run starts, count) of lexicographically
 // SORTED key columns: count, scan and write on the current stream
 // (runs_multi.hip).  The outputs hold n entries; count is a 1-element
 // device tensor and the caller slices after one readback.
 std::tuple<std::vector<torch::Tensor>, torch::Tensor, torch::Tensor>
 runs_multi(std::vector<torch::Tensor> cols) {
-  const int64_t n = lex_cols(cols, "runs_multi");
+  const int64_t n =
+      int64_cols(cols, 1, MAX_KEY_COLS, "runs_multi: key columns");
   MrCols kc{};
   kc.n = (int)cols.size();
   std::vector<torch::Tensor> uniq;
@@ -1181,14 +1154,14 @@ runs_multi(std::vector<torch::Tensor> cols) {
   const int64_t ntiles = (n + MRUNS_TILE - 1) / MRUNS_TILE;
   TORCH_CHECK(ntiles < (1ll << 31), "runs_multi: batch too large");
   auto counts = torch::empty({ntiles}, cols[0].options());
-  MRUNS_LAUNCH(k_mruns_count, kc.n, (uint32_t)ntiles, MRUNS_BLOCK, kc, n,
-               counts.data_ptr<int64_t>());
+  LAUNCH_NK(k_mruns_count, kc.n, (uint32_t)ntiles, MRUNS_BLOCK, kc, n,
+            counts.data_ptr<int64_t>());
   // 1-D on purpose: a 2-D cumsum over dim 0 takes torch's strided
   // outer-dim scan (see tokenize_bytes)
   auto incl = at::cumsum(counts, 0);
-  MRUNS_LAUNCH(k_mruns_write, kc.n, (uint32_t)ntiles, MRUNS_BLOCK, kc, n,
-               (const int64_t*)incl.data_ptr<int64_t>(), n,
-               starts.data_ptr<int64_t>());
+  LAUNCH_NK(k_mruns_write, kc.n, (uint32_t)ntiles, MRUNS_BLOCK, kc, n,
+            (const int64_t*)incl.data_ptr<int64_t>(), n,
+            starts.data_ptr<int64_t>());
   return {uniq, starts, incl.slice(0, ntiles - 1, ntiles)};
 }
 
@@ -1198,8 +1171,10 @@ runs_multi(std::vector<torch::Tensor> cols) {
 torch::Tensor lex_searchsorted(std::vector<torch::Tensor> sorted_cols,
                                std::vector<torch::Tensor> query_cols,
                                bool right) {
-  const int64_t u = lex_cols(sorted_cols, "lex_searchsorted");
-  const int64_t m = lex_cols(query_cols, "lex_searchsorted");
+  const int64_t u = int64_cols(sorted_cols, 1, MAX_KEY_COLS,
+                               "lex_searchsorted: key columns");
+  const int64_t m = int64_cols(query_cols, 1, MAX_KEY_COLS,
+                               "lex_searchsorted: key columns");
   TORCH_CHECK(sorted_cols.size() == query_cols.size() &&
                   sorted_cols[0].device() == query_cols[0].device(),
               "lex_searchsorted: sorted and query tuples must have the "
@@ -1212,9 +1187,8 @@ torch::Tensor lex_searchsorted(std::vector<torch::Tensor> sorted_cols,
   }
   auto out = torch::empty({m}, query_cols[0].options());
   if (m == 0) return out;
-  const int blocks = (int)std::min<int64_t>((m + 255) / 256, 32768);
-  MRUNS_LAUNCH(k_lex_search, kc.n, blocks, 256, kc, u, m, (int)right,
-               out.data_ptr<int64_t>());
+  LAUNCH_NK(k_lex_search, kc.n, grid_blocks(m, 256), 256, kc, u, m,
+            (int)right, out.data_ptr<int64_t>());
   return out;
 }
 
@@ -1228,7 +1202,7 @@ torch::Tensor hash_bytes(torch::Tensor bytes, torch::Tensor offsets,
   int64_t n = offsets.size(0) - 1;
   auto out = torch::empty({n}, bytes.options().dtype(torch::kUInt32));
   if (n == 0) return out;
-  int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
+  int blocks = grid_blocks(n);
   hipLaunchKernelGGL(k_hash_bytes, dim3(blocks), dim3(THREADS), 0,
                      current_stream(), bytes.data_ptr<uint8_t>(),
                      offsets.data_ptr<int64_t>(), n, (uint32_t)seed,
@@ -1246,7 +1220,7 @@ torch::Tensor hash_bytes64(torch::Tensor bytes, torch::Tensor offsets,
   int64_t n = offsets.size(0) - 1;
   auto out = torch::empty({n}, bytes.options().dtype(torch::kInt64));
   if (n == 0) return out;
-  int blocks = (int)std::min<int64_t>((n + THREADS - 1) / THREADS, 32768);
+  int blocks = grid_blocks(n);
   hipLaunchKernelGGL(k_hash_bytes64, dim3(blocks), dim3(THREADS), 0,
                      current_stream(), bytes.data_ptr<uint8_t>(),
                      offsets.data_ptr<int64_t>(), n, (uint32_t)seed_hi,
@@ -1503,12 +1477,6 @@ int64_t idd_table(const torch::Tensor& tags, const torch::Tensor& ref) {
   return cap;
 }
 
-void idd_ids(const torch::Tensor& ids) {
-  TORCH_CHECK(ids.is_cuda() && ids.is_contiguous() && ids.dim() == 1 &&
-                  ids.scalar_type() == torch::kInt64,
-              "ids must be a contiguous int64 device tensor");
-}
-
 // Claim a slot for every id not yet in the table.  lens[i] is the byte
 // length of row i; counters is int64[3] = {new rows, new bytes, overflow},
 // zeroed by the caller.  Returns newrows int64[n]: its first counters[0]
@@ -1518,8 +1486,7 @@ torch::Tensor iddict_claim(torch::Tensor ids, torch::Tensor lens,
                            torch::Tensor tags, torch::Tensor ref,
                            int64_t base, torch::Tensor counters,
                            int64_t max_probes) {
-  idd_ids(ids);
-  const int64_t n = ids.size(0);
+  const int64_t n = int64_cols({ids}, 1, 1, "ids");
   const int64_t cap = idd_table(tags, ref);
   TORCH_CHECK(lens.is_cuda() && lens.is_contiguous() && lens.dim() == 1 &&
                   lens.scalar_type() == torch::kInt64 && lens.size(0) == n,
@@ -1531,7 +1498,7 @@ torch::Tensor iddict_claim(torch::Tensor ids, torch::Tensor lens,
   TORCH_CHECK(max_probes >= 1 && base >= 0);
   auto newrows = torch::empty({n}, ids.options());
   if (n == 0) return newrows;
-  hipLaunchKernelGGL(k_idd_claim, dim3(gbm_blocks(n)), dim3(THREADS), 0,
+  hipLaunchKernelGGL(k_idd_claim, dim3(grid_blocks(n)), dim3(THREADS), 0,
                      current_stream(), ids.data_ptr<int64_t>(), n,
                      lens.data_ptr<int64_t>(), tags.data_ptr<int64_t>(),
                      ref.data_ptr<int64_t>(), cap, base,
@@ -1545,13 +1512,12 @@ torch::Tensor iddict_claim(torch::Tensor ids, torch::Tensor lens,
 // The position of every id, -1 when absent.
 torch::Tensor iddict_lookup(torch::Tensor ids, torch::Tensor tags,
                             torch::Tensor ref, int64_t max_probes) {
-  idd_ids(ids);
-  const int64_t n = ids.size(0);
+  const int64_t n = int64_cols({ids}, 1, 1, "ids");
   const int64_t cap = idd_table(tags, ref);
   TORCH_CHECK(max_probes >= 1);
   auto out = torch::empty({n}, ids.options());
   if (n == 0) return out;
-  hipLaunchKernelGGL(k_idd_lookup, dim3(gbm_blocks(n)), dim3(THREADS), 0,
+  hipLaunchKernelGGL(k_idd_lookup, dim3(grid_blocks(n)), dim3(THREADS), 0,
                      current_stream(), ids.data_ptr<int64_t>(), n,
                      tags.data_ptr<int64_t>(), ref.data_ptr<int64_t>(), cap,
                      out.data_ptr<int64_t>(), max_probes);
@@ -1572,7 +1538,7 @@ void iddict_rehash(torch::Tensor old_tags, torch::Tensor old_ref,
                   overflow.numel() >= 1,
               "overflow must be int32[1]");
   TORCH_CHECK(max_probes >= 1);
-  hipLaunchKernelGGL(k_idd_rehash, dim3(gbm_blocks(old_cap)), dim3(THREADS),
+  hipLaunchKernelGGL(k_idd_rehash, dim3(grid_blocks(old_cap)), dim3(THREADS),
                      0, current_stream(), old_tags.data_ptr<int64_t>(),
                      old_ref.data_ptr<int64_t>(), old_cap,
                      new_tags.data_ptr<int64_t>(),
@@ -1608,7 +1574,7 @@ std::vector<torch::Tensor> bytes_gather(torch::Tensor data,
     return {torch::empty({0}, data.options()), out_offsets};
   auto stream = current_stream();
   auto lens = torch::empty({m}, offsets.options());
-  hipLaunchKernelGGL(k_bg_lens, dim3(gbm_blocks(m)), dim3(THREADS), 0,
+  hipLaunchKernelGGL(k_bg_lens, dim3(grid_blocks(m)), dim3(THREADS), 0,
                      stream, offsets.data_ptr<int64_t>(), n,
                      rows.data_ptr<int64_t>(), m, lens.data_ptr<int64_t>());
   HIP_CHECK(hipGetLastError());

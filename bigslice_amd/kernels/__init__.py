@@ -38,28 +38,36 @@ def _require(feature: str):
             f"import error: {_load_error!r}")
 
 
+def native(on_gpu: bool, feature: str) -> bool:
+    """The extension gate: whether `feature` runs in the extension.  True
+    with the extension loaded and the input on a GPU.  Without it, an
+    input on a GPU raises (no silent eager fallback) unless
+    BIGSLICE_ALLOW_EAGER_FALLBACK=1; everything else takes the torch
+    path.  The flag and the module are looked up on every call."""
+    if _C is not None:
+        return bool(on_gpu)
+    if on_gpu and not ALLOW_FALLBACK:
+        _require(feature)
+    return False
+
+
 # -- hashing --------------------------------------------------------------
 
 def hash_columns_device(cols: List[torch.Tensor], seed: int) -> torch.Tensor:
     """murmur3-32 XOR-combined over key columns; returns uint32 tensor."""
-    if _C is None and ALLOW_FALLBACK:
+    if not native(True, "hash_columns"):
         from .. import hashing
         host = [c.cpu() for c in cols]
         return hashing.hash_columns(host, seed).to(cols[0].device)
-    _require("hash_columns")
     return _C.hash_columns(cols, seed)
 
 
 # -- partition (K4) -------------------------------------------------------
 
 def partition_supported(frame) -> bool:
-    if _C is None:
-        if not ALLOW_FALLBACK:
-            # no silent eager fallback on a GPU box (the HIP path must
-            # be the one that runs)
-            _require("partition_frame")
-        return False
-    return all(isinstance(c, torch.Tensor) for c in frame.columns)
+    # (asked only of frames of a GPU session)
+    return native(True, "partition_frame") and all(
+        isinstance(c, torch.Tensor) for c in frame.columns)
 
 
 def partition_frame(frame, num_partitions: int, partitioner):
@@ -93,8 +101,8 @@ def partition_frame(frame, num_partitions: int, partitioner):
 from .groupby import (  # noqa: E402,F401
     _AGG_CODES, _GB_KEY_DTYPES, _GB_VAL_DTYPES, GB_SENTINEL, MAX_PROBES,
     PART_LDS_SLOTS, PART_MAX_BUCKETS, PART_OWN_LIMIT, PART_TILE_ROWS,
-    GroupTable, _next_pow2, groupby, groupby_supported, part_buckets,
-    part_owned_buckets)
+    GroupTable, _next_pow2, groupby, groupby_shape_supported,
+    groupby_supported, part_buckets, part_owned_buckets)
 
 # -- group-by aggregate over multi-column integer keys (K21) ---------------
 
@@ -114,18 +122,14 @@ def sort_pairs_supported(keys: torch.Tensor) -> bool:
 
 def radix_argsort(keys: torch.Tensor) -> torch.Tensor:
     """Device radix sort; returns the sorting permutation (int64)."""
-    if _C is None:
-        if keys.is_cuda and not ALLOW_FALLBACK:
-            _require("radix_argsort")
+    if not native(keys.is_cuda, "radix_argsort"):
         return torch.argsort(keys, stable=True)
     return _C.radix_argsort(keys)
 
 
 def radix_sort_kv(keys: torch.Tensor, val: torch.Tensor):
     """Direct (key, value) radix sort for one 8-byte value column."""
-    if _C is None:
-        if keys.is_cuda and not ALLOW_FALLBACK:
-            _require("radix_sort_kv")
+    if not native(keys.is_cuda, "radix_sort_kv"):
         perm = torch.argsort(keys, stable=True)
         return keys[perm], val[perm]
     v64 = val.view(torch.int64) if val.dtype != torch.int64 else val
@@ -135,9 +139,7 @@ def radix_sort_kv(keys: torch.Tensor, val: torch.Tensor):
 
 def radix_sort_keys(keys: torch.Tensor) -> torch.Tensor:
     """Device radix key-only sort (no permutation)."""
-    if _C is None:
-        if keys.is_cuda and not ALLOW_FALLBACK:
-            _require("radix_sort_keys")
+    if not native(keys.is_cuda, "radix_sort_keys"):
         return torch.sort(keys).values
     return _C.radix_sort_keys(keys)
 
@@ -159,9 +161,7 @@ def expr_supported(program, frame) -> bool:
     cols = [frame.columns[i] for i in program.inputs]
     on_gpu = any(isinstance(c, torch.Tensor) and c.is_cuda
                  for c in frame.columns)
-    if _C is None:
-        if on_gpu and not ALLOW_FALLBACK:
-            _require("expr_apply")
+    if not native(on_gpu, "expr_apply"):
         return False
     # (a column whose dtype is not the schema's the program was typed
     # from also takes the eval path, where torch promotes what it sees)

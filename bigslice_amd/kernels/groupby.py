@@ -17,7 +17,8 @@ from typing import List, Optional
 
 import torch
 
-from . import _C, ALLOW_FALLBACK, _require
+from .. import kernels as _k
+from . import _C, native
 from .sortedkeys import sort_combine
 
 _AGG_CODES = {"sum": 0, "min": 1, "max": 2, "prod": 3}
@@ -68,11 +69,19 @@ class Options:
             debug=bool(env.get("BIGSLICE_GB_DEBUG")))
 
 
-def _next_pow2(n: int) -> int:
-    c = 1024
+def _next_pow2(n: int, floor: int = 1024) -> int:
+    c = floor
     while c < n:
         c <<= 1
     return c
+
+
+def first_capacity(cap_hint: Optional[int], n: int, floor: int = 1024) -> int:
+    """Capacity of a table whose first batch has n rows: the caller's
+    hint, else two slots per row up to config.GROUPBY_INITIAL_CAP."""
+    from .. import config
+    return _next_pow2(cap_hint or min(
+        2 * n, getattr(config, "GROUPBY_INITIAL_CAP", 1 << 23)), floor)
 
 
 def part_buckets(n: int, nkeys: float, cap: int,
@@ -214,18 +223,53 @@ def regrow_capacity(cap: int, rows: int) -> int:
 
 def groupby_supported(keys: torch.Tensor, vals: List[torch.Tensor],
                       aggs: List[str]) -> bool:
-    if _C is None:
-        if keys.is_cuda and not ALLOW_FALLBACK:
-            _require("groupby")
-        return False
-    if keys.dtype not in _GB_KEY_DTYPES:
-        return False
-    if not all(v.dtype in _GB_VAL_DTYPES for v in vals):
-        return False
-    return all(a in _AGG_CODES for a in aggs)
+    return (native(keys.is_cuda, "groupby") and groupby_shape_supported(
+        [keys.dtype], [v.dtype for v in vals], aggs))
 
 
-class GroupTable:
+def groupby_shape_supported(key_dtypes, val_dtypes, aggs) -> bool:
+    """Shapes GroupTable takes: one int64 key column, the plain insert's
+    value dtypes and aggregations."""
+    return (all(dt in _GB_KEY_DTYPES for dt in key_dtypes)
+            and all(dt in _GB_VAL_DTYPES for dt in val_dtypes)
+            and all(isinstance(a, str) and a in _AGG_CODES for a in aggs))
+
+
+class HashTable:
+    """The lifecycle GroupTable and MultiKeyTable share: capacity from
+    the first batch, batches retained, one readback per compaction, and
+    a probe-chain overflow answered by a larger table and a re-insert.
+    A subclass has _alloc(cap), _insert_now(keys, vals), _slots() and the
+    attributes device, val_dtypes, codes, cap, cap_hint, flags, batches
+    and rows."""
+
+    def _ensure_alloc(self, n: int):
+        if self.cap is None:
+            self._alloc(first_capacity(self.cap_hint, n))
+
+    def _agg_arrays(self, cap: int) -> List:
+        """[cap + 1] aggregates per value column, at the identity."""
+        return [
+            _k._C.agg_identity(torch.empty(0, dtype=dt, device=self.device),
+                            code, cap + 1)
+            for dt, code in zip(self.val_dtypes, self.codes)]
+
+    def _compact(self):
+        """One compaction and its one readback: (outs, [count, *flags])."""
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        outs = _k._C.groupby_compact(*self._slots(), cursor)
+        host = torch.cat([cursor, self.flags.to(torch.int64)]).cpu()
+        return outs, host.tolist()
+
+    def _regrow(self):
+        batches = self.batches
+        self._alloc(regrow_capacity(self.cap, self.rows))
+        self.batches = []
+        for keys, vals in batches:
+            self._insert_now(keys, vals)
+
+
+class GroupTable(HashTable):
     """Streaming device hash-aggregate (K9): an open-addressing table in
     HBM that multiple batches insert into; finish() compacts used slots.
     On probe-chain overflow the table doubles and re-inserts all retained
@@ -274,11 +318,11 @@ class GroupTable:
         dev = self.device
         self.tkeys = torch.full((cap + 1,), GB_SENTINEL,
                                 dtype=torch.int64, device=dev)
-        self.tabs = [
-            _C.agg_identity(torch.empty(0, dtype=dt, device=dev), code,
-                            cap + 1)
-            for dt, code in zip(self.val_dtypes, self.codes)]
+        self.tabs = self._agg_arrays(cap)
         self.flags = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def _slots(self):
+        return self.tkeys, self.tabs
 
     @property
     def _sort_combinable(self) -> bool:
@@ -286,7 +330,7 @@ class GroupTable:
         numeric columns (its float sums are run-to-run reproducible —
         unlike the hash table's atomic adds).  These shapes defer their
         batches until a sampled cardinality has chosen the combine mode."""
-        return (_C is not None
+        return (_k._C is not None
                 and str(self.device).startswith("cuda")
                 and all(a in ("sum", "min", "max") for a in self.aggs)
                 and all(dt in _GB_VAL_DTYPES for dt in self.val_dtypes))
@@ -302,7 +346,7 @@ class GroupTable:
         prefix = min(keys.shape[0], self.opts.sample_rows)
         # probe=False: the probe's count readback would sync the
         # stream; the sample must stay fire-and-forget
-        sk = _C.radix_sort_keys(keys[:prefix].contiguous(),
+        sk = _k._C.radix_sort_keys(keys[:prefix].contiguous(),
                                 probe=False)
         self._sample_n = prefix
         self._sample_batch_n = keys.shape[0]
@@ -364,12 +408,7 @@ class GroupTable:
         the single int64 sum); every other state of _mode, undecided and
         "sort" (its merge into a provisional table) included, takes the
         plain one-pass insert."""
-        if self.cap is None:
-            from .. import config
-            hint = self.cap_hint or min(
-                2 * keys.shape[0],
-                getattr(config, "GROUPBY_INITIAL_CAP", 1 << 23))
-            self._alloc(_next_pow2(hint))
+        self._ensure_alloc(keys.shape[0])
         self.batches.append((keys, vals))
         mode = self._mode if self._sum_i64 else None
         plan = part_plan(
@@ -377,17 +416,17 @@ class GroupTable:
             PART_LDS_SLOTS, PART_TILE_ROWS, PART_MAX_BUCKETS,
             self._PART_MIN_ROWS) if mode == "part" else None
         if mode == "lds":
-            _C.groupby_insert_lds(keys, vals[0], self.tkeys, self.tabs[0],
+            _k._C.groupby_insert_lds(keys, vals[0], self.tkeys, self.tabs[0],
                                   self.flags, MAX_PROBES,
                                   self.opts.lds_blocks)
         elif plan is not None:
             kind, nbuckets = plan
-            _C.groupby_insert_part(keys, vals[0], self.tkeys, self.tabs[0],
+            _k._C.groupby_insert_part(keys, vals[0], self.tkeys, self.tabs[0],
                                    self.flags, MAX_PROBES, nbuckets,
                                    1 if kind == "owned" else 0,
                                    self.opts.part_group)
         else:
-            _C.groupby_insert(keys, list(vals), self.codes, self.tkeys,
+            _k._C.groupby_insert(keys, list(vals), self.codes, self.tkeys,
                               self.tabs, self.flags, MAX_PROBES)
 
     def _finish_deferred(self):
@@ -436,18 +475,9 @@ class GroupTable:
             return empty, [torch.empty(0, dtype=dt, device=self.device)
                            for dt in self.val_dtypes]
         while True:
-            cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-            outs = _C.groupby_compact(self.tkeys, self.tabs, cursor)
-            host = torch.cat([cursor,
-                              self.flags.to(torch.int64)]).cpu()
-            nkeys, sentinel_seen, overflow = (int(host[0]), int(host[1]),
-                                              int(host[2]))
+            outs, (nkeys, sentinel_seen, overflow) = self._compact()
             if overflow:
-                batches = self.batches
-                self._alloc(regrow_capacity(self.cap, self.rows))
-                self.batches = []
-                for keys, vals in batches:
-                    self._insert_now(keys, vals)
+                self._regrow()
                 continue
             keys = outs[0][:nkeys]
             vals = [o[:nkeys] for o in outs[1:]]

@@ -21,9 +21,10 @@ from typing import Callable, List, Optional, Sequence
 
 import torch
 
+from .. import kernels as _k
 from . import _C, _require
 from .groupby import (_AGG_CODES, _GB_VAL_DTYPES, GB_SENTINEL, MAX_PROBES,
-                      _next_pow2, regrow_capacity)
+                      HashTable)
 
 # csrc/columns.h: most key columns, and most key + value columns (what
 # groupby_compact takes)
@@ -106,7 +107,7 @@ def multikey_supported(key_dtypes, val_dtypes, aggs) -> bool:
             and all(isinstance(a, str) and a in _AGG_CODES for a in aggs))
 
 
-class MultiKeyTable:
+class MultiKeyTable(HashTable):
     """Streaming device hash-aggregate keyed by a tuple of integer
     columns.  Follows GroupTable: batches are retained, a probe-chain
     overflow is noticed at finish() and answered by regrowing and
@@ -148,11 +149,11 @@ class MultiKeyTable:
                                device=dev)
         self.kcols = [torch.empty(cap + 1, dtype=torch.int64, device=dev)
                       for _ in range(self.nkey)]
-        self.tabs = [
-            _C.agg_identity(torch.empty(0, dtype=dt, device=dev), code,
-                            cap + 1)
-            for dt, code in zip(self.val_dtypes, self.codes)]
+        self.tabs = self._agg_arrays(cap)
         self.flags = torch.zeros(3, dtype=torch.int32, device=dev)
+
+    def _slots(self):
+        return self.tags, self.kcols + self.tabs
 
     def insert(self, keys: List[torch.Tensor], vals: List[torch.Tensor]):
         if len(keys) != self.nkey or len(vals) != len(self.val_dtypes):
@@ -173,14 +174,9 @@ class MultiKeyTable:
                          [v.contiguous() for v in vals])
 
     def _insert_now(self, keys, vals):
-        if self.cap is None:
-            from .. import config
-            hint = self.cap_hint or min(
-                2 * keys[0].shape[0],
-                getattr(config, "GROUPBY_INITIAL_CAP", 1 << 23))
-            self._alloc(_next_pow2(hint))
+        self._ensure_alloc(keys[0].shape[0])
         self.batches.append((keys, vals))
-        _C.groupby_mk_insert(keys, vals, self.codes, self.tags, self.kcols,
+        _k._C.groupby_mk_insert(keys, vals, self.codes, self.tags, self.kcols,
                              self.tabs, self.flags, MAX_PROBES,
                              self.opts.fp_bits)
 
@@ -204,12 +200,7 @@ class MultiKeyTable:
                     [torch.empty(0, dtype=dt, device=self.device)
                      for dt in self.val_dtypes])
         while True:
-            cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-            outs = _C.groupby_compact(self.tags, self.kcols + self.tabs,
-                                      cursor)
-            host = torch.cat([cursor, self.flags.to(torch.int64)]).cpu()
-            ngroups, overflow, collision = (int(host[0]), int(host[2]),
-                                            int(host[3]))
+            outs, (ngroups, _, overflow, collision) = self._compact()
             if collision:
                 # Two tuples share a tag: the table holds one of them and
                 # skipped the other's rows.  Group the batches exactly.
@@ -228,11 +219,7 @@ class MultiKeyTable:
                 keys, vals = list(keys), list(vals)
                 break
             if overflow:
-                batches = self.batches
-                self._alloc(regrow_capacity(self.cap, self.rows))
-                self.batches = []
-                for keys, vals in batches:
-                    self._insert_now(keys, vals)
+                self._regrow()
                 continue
             keys = [o[:ngroups] for o in outs[1:1 + self.nkey]]
             vals = [o[:ngroups] for o in outs[1 + self.nkey:]]

@@ -20,17 +20,14 @@ from typing import List, Optional
 
 import torch
 
+from .. import kernels as _k
 from . import _C, _require
-from .groupby import GB_SENTINEL, MAX_PROBES
+from .groupby import GB_SENTINEL, MAX_PROBES, _next_pow2, first_capacity
 
 _MAX_CAP = 1 << 30  # capacity is a power of two below 2^31
 
 
-def _pow2(n: int, floor: int = 16) -> int:
-    c = floor
-    while c < n:
-        c <<= 1
-    return c
+_CAP_FLOOR = 16  # the smallest table
 
 
 def bytes_gather(data: torch.Tensor, offsets: torch.Tensor,
@@ -40,7 +37,7 @@ def bytes_gather(data: torch.Tensor, offsets: torch.Tensor,
     is the byte count of the result when the caller knows it; None reads
     it back (one host readback)."""
     _require("bytes_gather")
-    out = _C.bytes_gather(data.contiguous(), offsets.contiguous(), rows,
+    out = _k._C.bytes_gather(data.contiguous(), offsets.contiguous(), rows,
                           -1 if total is None else int(total))
     return out[0], out[1]
 
@@ -87,7 +84,7 @@ class IdDictionary:
         while True:
             tags, ref = self._alloc(cap)
             flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-            _C.iddict_rehash(self.tags, self.ref, tags, ref, flag,
+            _k._C.iddict_rehash(self.tags, self.ref, tags, ref, flag,
                              self._probes(cap))
             if not int(flag.item()):  # only on the regrow path
                 break
@@ -112,15 +109,12 @@ class IdDictionary:
             return self._add_host(ids, col)
         ids = ids.contiguous()
         if self.cap is None:
-            from .. import config
-            hint = self.cap_hint or min(
-                2 * n, getattr(config, "GROUPBY_INITIAL_CAP", 1 << 23))
-            self.cap = _pow2(hint)
+            self.cap = first_capacity(self.cap_hint, n, _CAP_FLOOR)
             self.tags, self.ref = self._alloc(self.cap)
         lens = col.lengths().contiguous()
         while True:
             counters = torch.zeros(3, dtype=torch.int64, device=self.device)
-            newrows = _C.iddict_claim(ids, lens, self.tags, self.ref,
+            newrows = _k._C.iddict_claim(ids, lens, self.tags, self.ref,
                                       self._n, counters,
                                       self._probes(self.cap))
             # the one host readback per run of the claim
@@ -135,9 +129,10 @@ class IdDictionary:
             # Rows were left out.  Regrow and run the claim over the same
             # batch again: the rows of this run are found, the rest are
             # appended after them.
-            self._regrow(max(2 * self.cap, _pow2(4 * self._n)))
+            self._regrow(max(2 * self.cap,
+                             _next_pow2(4 * self._n, _CAP_FLOOR)))
         if 2 * self._n > self.cap:
-            self._regrow(_pow2(4 * self._n))
+            self._regrow(_next_pow2(4 * self._n, _CAP_FLOOR))
 
     def lookup(self, ids: torch.Tensor) -> torch.Tensor:
         """The position of every id, -1 when absent."""
@@ -146,7 +141,7 @@ class IdDictionary:
         ids = ids.to(self.device).contiguous()
         if self.cap is None:
             return torch.full_like(ids, -1)
-        return _C.iddict_lookup(ids, self.tags, self.ref,
+        return _k._C.iddict_lookup(ids, self.tags, self.ref,
                                 self._probes(self.cap))
 
     def strings(self):

@@ -25,6 +25,7 @@ device, arbitrary callables run on host.
 
 from __future__ import annotations
 
+import functools
 import operator
 import os
 from typing import Callable, List, Optional, Sequence, Union
@@ -43,8 +44,6 @@ _CALLABLE_MAP = {
     min: "min",
     max: "max",
 }
-
-_SCATTER_OP = {"sum": "sum", "min": "amin", "max": "amax", "prod": "prod"}
 
 
 def resolve_agg(fn: Union[str, Callable]) -> Union[str, Callable]:
@@ -101,14 +100,54 @@ def make_aggregator(schema: Schema, agg: Aggregation, device: str,
             and not any(is_object(d) or is_bytes(d)
                         for d in schema.dtypes[1:])):
         return BytesKeyAggregator(schema, agg, device)
+    from .. import kernels
     if device.startswith("cuda") and bytes_tuple_supported(schema, agg) \
-            and os.environ.get("BIGSLICE_GB_BYTES_MULTIKEY", "1") != "0":
-        from .. import kernels
-        if kernels.have_extension():
-            return BytesTupleAggregator(schema, agg, device)
-        if not kernels.ALLOW_FALLBACK:
-            kernels._require("groupby")  # no silent eager fallback
+            and os.environ.get("BIGSLICE_GB_BYTES_MULTIKEY", "1") != "0" \
+            and kernels.native(True, "groupby"):
+        return BytesTupleAggregator(schema, agg, device)
     return DictAggregator(schema, agg)
+
+
+# Small device frames are concatenated before a table is touched: one set
+# of launches instead of many (consumer-side shuffle buckets are ~100k
+# rows).
+_SMALL_ROWS = 1 << 20
+
+
+class _Pending:
+    """Frames waiting to go on as one."""
+
+    def __init__(self):
+        self.frames: List[Frame] = []
+        self.rows = 0
+
+    def add(self, frame: Frame) -> None:
+        self.frames.append(frame)
+        self.rows += len(frame)
+
+    def take(self) -> Optional[Frame]:
+        """The waiting frames as one (None without any); none wait after."""
+        if not self.frames:
+            return None
+        f = Frame.concat(self.frames)
+        self.frames.clear()
+        self.rows = 0
+        return f
+
+    def flush(self, sink) -> None:
+        f = self.take()
+        if f is not None:
+            sink(f)
+
+    def feed(self, frame: Frame, sink) -> None:
+        """A frame of _SMALL_ROWS rows or more goes to sink at once; a
+        smaller one waits until four times as many rows do."""
+        if len(frame) >= _SMALL_ROWS:
+            sink(frame)
+            return
+        self.add(frame)
+        if self.rows >= 4 * _SMALL_ROWS:
+            self.flush(sink)
 
 
 def bytes_tuple_supported(schema: Schema, agg: Aggregation) -> bool:
@@ -147,10 +186,6 @@ class BytesTupleAggregator:
     is tested without a GPU.
     """
 
-    # small frames are concatenated before either table is touched, as
-    # in TensorAggregator: one set of launches instead of many
-    _SMALL_ROWS = 1 << 20
-
     def __init__(self, schema: Schema, agg: Aggregation, device: str):
         from ..kernels.iddict import IdDictionary
         from ..schema import Schema as S
@@ -166,29 +201,15 @@ class BytesTupleAggregator:
                           for i, dt in enumerate(schema.dtypes))
         self.inner = TensorAggregator(S(inner_dts, self.nkey), agg, device)
         self.dicts = {i: IdDictionary(device) for i in self.bytes_cols}
-        self._pending: List[Frame] = []
-        self._pending_rows = 0
+        # in front of the inner aggregator's: both tables see one frame
+        self._pending = _Pending()
 
     def add(self, frame: Frame) -> None:
         if len(frame) == 0:
             return
         if frame.device != self.device:
             frame = frame.to(self.device)
-        if len(frame) < self._SMALL_ROWS:
-            self._pending.append(frame)
-            self._pending_rows += len(frame)
-            if self._pending_rows >= 4 * self._SMALL_ROWS:
-                self._flush_pending()
-            return
-        self._insert(frame)
-
-    def _flush_pending(self) -> None:
-        if not self._pending:
-            return
-        f = Frame.concat(self._pending)
-        self._pending.clear()
-        self._pending_rows = 0
-        self._insert(f)
+        self._pending.feed(frame, self._insert)
 
     def _insert(self, f: Frame) -> None:
         cols = list(f.columns)
@@ -199,7 +220,7 @@ class BytesTupleAggregator:
         self.inner.add(Frame(cols, self.nkey))
 
     def result_frames(self, chunk: int):
-        self._flush_pending()
+        self._pending.flush(self._insert)
         first = True
         for f in self.inner.result_frames(chunk):
             if first:
@@ -289,8 +310,7 @@ class TensorAggregator:
         self.device = device
         self.keys: Optional[List[torch.Tensor]] = None
         self.vals: List[torch.Tensor] = []
-        self._pending: List[Frame] = []
-        self._pending_rows = 0
+        self._pending = _Pending()
         # Pre-combined passthrough: while every added frame carries the
         # SAME combiner instance id, its keys are globally unique and
         # re-aggregation is the identity (the machine-combiners
@@ -299,40 +319,27 @@ class TensorAggregator:
         # demotes everything to normal aggregation.
         self._pt_frames: Optional[List[Frame]] = []
         self._pt_id = None
-        # Device fast path: stream batches straight into the HIP
-        # GroupTable (no host sync until finish).
+        # Device fast path: stream batches straight into the HIP table
+        # of the key's width (no host sync until finish).
         self._table = None
-        if device.startswith("cuda") and self.nkey == 1:
-            from .. import kernels
-            val_dts = schema.dtypes[schema.prefix:]
-            shape_ok = (all(dt in kernels._GB_VAL_DTYPES
-                            for dt in val_dts)
-                        and schema.dtypes[0] in kernels._GB_KEY_DTYPES
-                        and all(isinstance(a, str) for a in agg.aggs))
-            if shape_ok and not kernels.have_extension() and \
-                    not kernels.ALLOW_FALLBACK:
-                kernels._require("groupby")  # no silent eager fallback
-            if shape_ok and kernels.have_extension():
-                self._table = kernels.GroupTable(val_dts, agg.aggs, device)
-        elif device.startswith("cuda") and self.nkey >= 2:
+        if device.startswith("cuda"):
             from .. import kernels
             from ..kernels import groupby_multi as gbm
-            val_dts = schema.dtypes[schema.prefix:]
-            shape_ok = (gbm.multikey_supported(
-                schema.dtypes[:schema.prefix], val_dts, agg.aggs)
-                and gbm.Options.from_env().enabled)
-            if shape_ok and not kernels.have_extension() and \
-                    not kernels.ALLOW_FALLBACK:
-                kernels._require("groupby")  # no silent eager fallback
-            if shape_ok and kernels.have_extension():
+            if self.nkey == 1:
+                supported = kernels.groupby_shape_supported
+                make = kernels.GroupTable
+            else:
+                def supported(*shape):
+                    return (gbm.multikey_supported(*shape)
+                            and gbm.Options.from_env().enabled)
                 # two tuples with one fingerprint: regroup exactly
-                self._table = gbm.MultiKeyTable(
-                    self.nkey, val_dts, agg.aggs, device,
+                make = functools.partial(
+                    gbm.MultiKeyTable, self.nkey,
                     fallback=lambda k, v: _combine_once(k, v, self.agg))
-
-    # small device batches are concatenated before insert: one launch
-    # instead of many (consumer-side shuffle buckets are ~100k rows)
-    _SMALL_ROWS = 1 << 20
+            val_dts = schema.dtypes[self.nkey:]
+            if supported(schema.dtypes[:self.nkey], val_dts, agg.aggs) \
+                    and kernels.native(True, "groupby"):
+                self._table = make(val_dts, agg.aggs, device)
 
     def add(self, frame: Frame) -> None:
         if len(frame) == 0:
@@ -354,26 +361,11 @@ class TensorAggregator:
 
     def _add_normal(self, frame: Frame) -> None:
         if self._table is not None:
-            if len(frame) < self._SMALL_ROWS:
-                self._pending.append(frame)
-                self._pending_rows += len(frame)
-                if self._pending_rows >= 4 * self._SMALL_ROWS:
-                    self._flush_table_pending()
-                return
-            self._table_insert(frame)
+            self._pending.feed(frame, self._table_insert)
             return
-        self._pending.append(frame)
-        self._pending_rows += len(frame)
-        if self._pending_rows >= config.COMBINER_TARGET_KEYS:
+        self._pending.add(frame)
+        if self._pending.rows >= config.COMBINER_TARGET_KEYS:
             self._flush()
-
-    def _flush_table_pending(self) -> None:
-        if not self._pending:
-            return
-        f = Frame.concat(self._pending)
-        self._pending.clear()
-        self._pending_rows = 0
-        self._table_insert(f)
 
     def _table_insert(self, f: Frame) -> None:
         vals = [c.contiguous() for c in f.columns[self.nkey:]]
@@ -383,11 +375,9 @@ class TensorAggregator:
             self._table.insert(list(f.columns[:self.nkey]), vals)
 
     def _flush(self) -> None:
-        if not self._pending:
+        f = self._pending.take()
+        if f is None:
             return
-        f = Frame.concat(self._pending)
-        self._pending.clear()
-        self._pending_rows = 0
         keys = [c for c in f.columns[: self.nkey]]
         vals = list(f.columns[self.nkey:])
         if self.keys is not None:
@@ -402,7 +392,7 @@ class TensorAggregator:
                 yield f
             return
         if self._table is not None:
-            self._flush_table_pending()
+            self._pending.flush(self._table_insert)
             keys, vals = self._table.finish()
             keys = [keys] if self.nkey == 1 else keys
             if keys[0].shape[0]:
@@ -430,6 +420,8 @@ def _combine_once(keys: List[torch.Tensor], vals: List[torch.Tensor],
     lexicographic stable sort + boundary detection), which runs on both
     CPU and GPU.
     """
+    from ..kernels.groupby import _AGG_CODES
+    from ..kernels.sortedkeys import _SCATTER_OP
     if len(keys) == 1:
         k = keys[0]
         if k.is_cuda:
@@ -462,8 +454,8 @@ def _combine_once(keys: List[torch.Tensor], vals: List[torch.Tensor],
     out_vals = []
     for v, a in zip(vals, agg.aggs):
         init = torch.empty(nseg, dtype=v.dtype, device=v.device)
-        out = init.scatter_reduce_(0, inv, v, reduce=_SCATTER_OP[a],
-                                   include_self=False)
+        out = init.scatter_reduce_(
+            0, inv, v, reduce=_SCATTER_OP[_AGG_CODES[a]], include_self=False)
         out_vals.append(out)
     return uks, out_vals
 

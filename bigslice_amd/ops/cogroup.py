@@ -18,7 +18,9 @@ from __future__ import annotations
 import os
 from typing import List
 
-from ..frame import Frame
+import torch
+
+from ..frame import Frame, SegmentedColumn
 from ..schema import OBJECT, Schema, common_key_schema
 from ..sliceio import IterReader, Reader
 from .slice_base import Dep, Name, Slice, TaskContext
@@ -45,25 +47,15 @@ class Cogroup(Slice):
             Schema(out_dts, nkey), num_shards,
             deps=[Dep(s, shuffle=True) for s in slices],
             name=Name("cogroup"))
+        self._device_shape = self._device_shape_ok()
 
     def reader(self, shard, dep_readers, ctx: TaskContext) -> Reader:
         nkey = self.schema.prefix
         val_counts = self._val_counts
-        # Device fast path: single int64 key, numeric value columns ->
-        # sort-merge cogroup on device with SegmentedColumn outputs.
-        import torch as _t
-        if (ctx.device != "cpu" and nkey == 1
-                and self.deps[0].slice.schema.dtypes[0] == _t.int64
-                and all(dt != OBJECT
-                        for d in self.deps for dt in d.slice.schema.dtypes)):
+        # Device fast path: sort-merge cogroup on device with
+        # SegmentedColumn outputs.
+        if ctx.device != "cpu" and self._device_eligible():
             return IterReader(self._device_gen(dep_readers, ctx))
-        # Same path over a composite integer key (K22): lexicographic
-        # sort, tuple run boundaries and a tuple searchsorted.
-        # BIGSLICE_COGROUP_MULTIKEY=0 keeps such keys on the host path.
-        if (ctx.device != "cpu"
-                and os.environ.get("BIGSLICE_COGROUP_MULTIKEY", "1") != "0"
-                and self._multikey_eligible()):
-            return IterReader(self._device_multi_gen(dep_readers, ctx))
 
         def gen():
             # Group each dep by key on the host: key -> [lists per column]
@@ -99,125 +91,108 @@ class Cogroup(Slice):
                 yield Frame.from_lists(out_cols, schema=self.schema)
         return IterReader(gen())
 
-    def _multikey_eligible(self) -> bool:
-        """Shapes the composite-key device path takes on a GPU session:
-        2..MAX_KEY_COLS int64/int32 key columns and dense torch columns
-        otherwise.  A missing extension is an error there, unless the
-        eager fallback is allowed; then the host path runs."""
-        import torch
+    def _device_shape_ok(self) -> bool:
+        """Shapes the device path takes.  One key column: int64, and no
+        OBJECT column in any dep.  A composite key (K22): int64/int32
+        key columns (at most MAX_KEY_COLS, checked with the extension's
+        constant when the reader is made) and dense torch columns
+        otherwise."""
+        nkey = self.schema.prefix
+        dep_dts = [d.slice.schema.dtypes for d in self.deps]
+        if nkey == 1:
+            return (dep_dts[0][0] == torch.int64
+                    and all(dt != OBJECT for dts in dep_dts for dt in dts))
+        return all(
+            all(dt in (torch.int64, torch.int32) for dt in dts[:nkey])
+            and all(isinstance(dt, torch.dtype) for dt in dts[nkey:])
+            for dts in dep_dts)
 
+    def _device_eligible(self) -> bool:
+        """Whether a GPU session's reader takes the device path: the
+        shape fits and, for a composite key, BIGSLICE_COGROUP_MULTIKEY is
+        not 0 and the extension is there (missing, it is an error unless
+        the eager fallback is allowed; then the host path runs).  A
+        single key costs its reader nothing here: its eight shards share
+        the interpreter and the path is host-bound on small inputs."""
+        if not self._device_shape or self.schema.prefix == 1:
+            return self._device_shape
+        if os.environ.get("BIGSLICE_COGROUP_MULTIKEY", "1") == "0":
+            return False
         from .. import kernels
         from ..kernels.groupby_multi import MAX_KEY_COLS
+        return (self.schema.prefix <= MAX_KEY_COLS
+                and kernels.native(True, "cogroup over multi-column keys"))
+
+    def _device_gen(self, dep_readers, ctx):
+        """Sort-merge cogroup over a key of nkey integer columns."""
+        from ..kernels import sortedkeys as sk
+        from ..sortio import sort_frame
+
+        device = ctx.device
         nkey = self.schema.prefix
-        if not 2 <= nkey <= MAX_KEY_COLS:
-            return False
-        for d in self.deps:
-            dts = d.slice.schema.dtypes
-            if not all(dt in (torch.int64, torch.int32)
-                       for dt in dts[:nkey]):
-                return False
-            if not all(isinstance(dt, torch.dtype) for dt in dts[nkey:]):
-                return False
-        if not kernels.have_extension():
-            if not kernels.ALLOW_FALLBACK:
-                kernels._require("cogroup over multi-column keys")
-            return False
-        return True
+        # 1. sort each dep side by key once.  One key column: the direct
+        # (key, value) radix sort for one 8-byte value column, a radix
+        # argsort and a gather otherwise; tuples: lexicographically.
+        def by_key(f):
+            if nkey == 1:
+                return sort_frame(f)
+            return f.select(sk.lex_argsort(f.columns[:nkey]))
+        sorted_deps = []
+        for r in dep_readers:
+            frames = [f for f in r if len(f)]
+            # (the concatenation is not kept: it is as large as the dep)
+            sorted_deps.append(by_key(Frame.concat(frames))
+                               if frames else None)
+        dep_runs = [(sk.runs_multi(sd.columns[:nkey]) if sd is not None
+                     else None) for sd in sorted_deps]
+        uniq_tuples = [r[0] for r in dep_runs if r is not None]
+        if not uniq_tuples:
+            return
+        # 2. sorted-unique union of the per-dep DISTINCT keys (tiny next
+        # to the row counts); a sort only with three or more deps
+        if len(uniq_tuples) == 1:
+            union_cols = uniq_tuples[0]
+        elif len(uniq_tuples) == 2:
+            union_cols = sk.merge_sorted_unique_multi(*uniq_tuples)
+        else:
+            union_cols = sk.unique_sorted_multi(sk.lex_sort_keys(
+                [torch.cat(cs) for cs in zip(*uniq_tuples)]))
+        # 3. per-dep segments over the sorted values
+        u = union_cols[0].shape[0]
+        out_cols = list(union_cols)
+        for di, sd in enumerate(sorted_deps):
+            if sd is not None:
+                out_cols.extend(_segments_for(
+                    dep_runs[di], sd.columns[nkey:], union_cols,
+                    sk.lex_searchsorted))
+            else:
+                empty_vals = [
+                    torch.empty(0, dtype=dt, device=device)
+                    for dt in self.deps[di].slice.schema.dtypes[nkey:]]
+                zeros = torch.zeros(u, dtype=torch.int64, device=device)
+                out_cols.extend(SegmentedColumn(ev, zeros, zeros)
+                                for ev in empty_vals)
+        frame = Frame(out_cols, prefix=nkey)
+        for off in range(0, len(frame), ctx.chunk):
+            yield frame.slice(off, min(off + ctx.chunk, len(frame)))
 
 
 def _key_sort(k):
     return k
 
 
-def _segments_for(run, value_cols, union_keys):
-    """Per-value-column SegmentedColumns aligned with union_keys,
-    built from the dep's precomputed runs.  Keys the dep lacks get
-    (0, 0) = empty segments."""
-    import torch
-
-    from ..frame import SegmentedColumn
-
-    uniq, starts, ends = run
-    u = union_keys.shape[0]
-    if uniq.shape[0] != u:
-        # uniq is a subset of union of equal sortedness; sizes equal
-        # implies identical key sets, so scatter only when they differ
-        idx = torch.searchsorted(union_keys, uniq)
-        s = torch.zeros(u, dtype=torch.int64, device=union_keys.device)
-        e = torch.zeros(u, dtype=torch.int64, device=union_keys.device)
-        s[idx] = starts
-        e[idx] = ends
-        starts, ends = s, e
-    return [SegmentedColumn(v.contiguous(), starts, ends)
-            for v in value_cols]
-
-
-# Attach the device generator to Cogroup (kept separate for readability).
-def _cogroup_device_gen(self, dep_readers, ctx):
-    import torch
-
-    from ..frame import Frame, SegmentedColumn
-
-    from ..sortio import sort_frame
-    from .. import kernels
-    from ..kernels.sortedkeys import merge_sorted_unique, runs, unique_sorted
-
-    device = ctx.device
-    # 1. sort each dep side by key once (direct kv radix for 2-column)
-    sorted_deps = []
-    for r in dep_readers:
-        frames = [f for f in r]
-        sorted_deps.append(sort_frame(Frame.concat(frames))
-                           if frames else None)
-    dep_runs = [(runs(sd.columns[0].contiguous()) if sd is not None
-                 else None) for sd in sorted_deps]
-    uniq_arrays = [r[0] for r in dep_runs if r is not None]
-    if not uniq_arrays:
-        return
-    # 2. sorted-unique union of the per-dep DISTINCT keys (tiny next
-    # to the row counts); radix only as a multi-dep fallback
-    if len(uniq_arrays) == 1:
-        union_keys = uniq_arrays[0]
-    elif len(uniq_arrays) == 2:
-        union_keys = merge_sorted_unique(uniq_arrays[0], uniq_arrays[1])
-    else:
-        union_keys = unique_sorted(
-            kernels.radix_sort_keys(torch.cat(uniq_arrays)))
-    # 3. per-dep segments over the sorted values
-    out_cols = [union_keys]
-    for di, sd in enumerate(sorted_deps):
-        if sd is not None:
-            out_cols.extend(_segments_for(dep_runs[di], sd.columns[1:],
-                                          union_keys))
-        else:
-            empty_vals = [torch.empty(0, dtype=dt, device=device)
-                          for dt in self.deps[di].slice.schema.dtypes[1:]]
-            zeros = torch.zeros(union_keys.shape[0], dtype=torch.int64,
-                                device=device)
-            out_cols.extend(SegmentedColumn(ev, zeros, zeros)
-                            for ev in empty_vals)
-    frame = Frame(out_cols, prefix=1)
-    for off in range(0, len(frame), ctx.chunk):
-        yield frame.slice(off, min(off + ctx.chunk, len(frame)))
-
-
-Cogroup._device_gen = _cogroup_device_gen
-
-
-def _segments_for_multi(run, value_cols, union_cols):
-    """_segments_for over tuple keys: the dep's runs scatter to their
-    positions among the union's tuples, found by lex_searchsorted."""
-    import torch
-
-    from ..frame import SegmentedColumn
-    from ..kernels.sortedkeys import lex_searchsorted
-
+def _segments_for(run, value_cols, union_cols, search):
+    """Per-value-column SegmentedColumns aligned with the union's key
+    tuples, built from the dep's precomputed runs; search is
+    sortedkeys.lex_searchsorted.  Keys the dep lacks get (0, 0) = empty
+    segments."""
     uniq_cols, starts, ends = run
     u = union_cols[0].shape[0]
     if uniq_cols[0].shape[0] != u:
-        # a subset of the union, in the same order (see _segments_for)
+        # uniq is a subset of union of equal sortedness; sizes equal
+        # implies identical key sets, so scatter only when they differ
         dev = union_cols[0].device
-        idx = lex_searchsorted(union_cols, uniq_cols)
+        idx = search(union_cols, uniq_cols)
         s = torch.zeros(u, dtype=torch.int64, device=dev)
         e = torch.zeros(u, dtype=torch.int64, device=dev)
         s[idx] = starts
@@ -225,58 +200,3 @@ def _segments_for_multi(run, value_cols, union_cols):
         starts, ends = s, e
     return [SegmentedColumn(v.contiguous(), starts, ends)
             for v in value_cols]
-
-
-def _cogroup_device_multi_gen(self, dep_readers, ctx):
-    """_cogroup_device_gen, step by step, for a key of nkey columns."""
-    import torch
-
-    from ..frame import Frame, SegmentedColumn
-    from ..kernels.sortedkeys import (lex_argsort, merge_sorted_unique_multi,
-                                      runs_multi, unique_sorted_multi)
-
-    device = ctx.device
-    nkey = self.schema.prefix
-    # 1. sort each dep side lexicographically by its key columns once
-    sorted_deps = []
-    for r in dep_readers:
-        frames = [f for f in r if len(f)]
-        if not frames:
-            sorted_deps.append(None)
-            continue
-        f = Frame.concat(frames)
-        sorted_deps.append(f.select(lex_argsort(f.columns[:nkey])))
-    dep_runs = [(runs_multi(sd.columns[:nkey]) if sd is not None else None)
-                for sd in sorted_deps]
-    uniq_tuples = [r[0] for r in dep_runs if r is not None]
-    if not uniq_tuples:
-        return
-    # 2. sorted-unique union of the per-dep DISTINCT tuples
-    if len(uniq_tuples) == 1:
-        union_cols = uniq_tuples[0]
-    elif len(uniq_tuples) == 2:
-        union_cols = merge_sorted_unique_multi(uniq_tuples[0],
-                                               uniq_tuples[1])
-    else:
-        cat = [torch.cat(cs) for cs in zip(*uniq_tuples)]
-        perm = lex_argsort(cat)
-        union_cols = unique_sorted_multi([c[perm] for c in cat])
-    # 3. per-dep segments over the sorted values
-    u = union_cols[0].shape[0]
-    out_cols = list(union_cols)
-    for di, sd in enumerate(sorted_deps):
-        if sd is not None:
-            out_cols.extend(_segments_for_multi(
-                dep_runs[di], sd.columns[nkey:], union_cols))
-        else:
-            empty_vals = [torch.empty(0, dtype=dt, device=device)
-                          for dt in self.deps[di].slice.schema.dtypes[nkey:]]
-            zeros = torch.zeros(u, dtype=torch.int64, device=device)
-            out_cols.extend(SegmentedColumn(ev, zeros, zeros)
-                            for ev in empty_vals)
-    frame = Frame(out_cols, prefix=nkey)
-    for off in range(0, len(frame), ctx.chunk):
-        yield frame.slice(off, min(off + ctx.chunk, len(frame)))
-
-
-Cogroup._device_multi_gen = _cogroup_device_multi_gen

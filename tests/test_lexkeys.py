@@ -146,3 +146,83 @@ def test_merge_sorted_unique_multi_disjoint_and_equal():
     assert _tuples(got) == sorted(a + b)
     same = sk.merge_sorted_unique_multi(_cols(a, 2), _cols(a, 2))
     assert _tuples(same) == a
+
+
+# -- one column is a case of the tuple forms ---------------------------------
+
+ONE_COLUMN = {
+    "empty": ([], torch.int64),
+    "one row": ([5], torch.int64),
+    "all equal": ([7] * 33, torch.int64),
+    "all distinct": (list(range(-20, 21)), torch.int64),
+    "int32": ([-3, -3, 0, 2, 2, 2, 9], torch.int32),
+    "extremes": ([INT64_MIN, INT64_MIN, INT64_MAX, INT64_MAX],
+                 torch.int64),
+    "mixed": ([INT64_MIN, -1, -1, 0, 4, 4, 4, INT64_MAX], torch.int64),
+}
+
+
+def _one(name):
+    vals, dt = ONE_COLUMN[name]
+    return torch.tensor(vals, dtype=dt)
+
+
+def _same(got, want):
+    assert got.dtype == want.dtype
+    assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("name", list(ONE_COLUMN))
+def test_one_column_runs_equal_the_scalar_functions(name):
+    k = _one(name)
+    uniq, starts, ends = sk.runs_multi([k])
+    assert len(uniq) == 1
+    su, ss, se = sk.runs(k)
+    _same(uniq[0], su)
+    _same(starts, ss)
+    _same(ends, se)
+    _same(sk.unique_sorted_multi([k])[0], sk.unique_sorted(k))
+    # and an oracle that is not the code under test
+    want_u, counts = torch.unique_consecutive(k, return_counts=True)
+    _same(uniq[0], want_u)
+    _same(ends, torch.cumsum(counts, 0))
+    _same(starts, torch.cumsum(counts, 0) - counts)
+    _same(sk.unique_sorted(k), want_u)
+
+
+@pytest.mark.parametrize("right", [False, True])
+@pytest.mark.parametrize("name", list(ONE_COLUMN))
+def test_one_column_search_is_torch_searchsorted(name, right):
+    s = _one(name)
+    for qname in ONE_COLUMN:
+        q = _one(qname).to(s.dtype)
+        _same(sk.lex_searchsorted([s], [q], right),
+              torch.searchsorted(s, q, right=right))
+
+
+@pytest.mark.parametrize("name", list(ONE_COLUMN))
+def test_one_column_merge_equals_the_scalar_function(name):
+    a = torch.unique_consecutive(_one(name))
+    for bname in ONE_COLUMN:
+        # (sorted again: narrowing the extremes to int32 reorders them)
+        b = torch.unique(_one(bname).to(a.dtype))
+        got = sk.merge_sorted_unique_multi([a], [b])
+        assert len(got) == 1
+        _same(got[0], sk.merge_sorted_unique(a, b))
+        _same(got[0], torch.unique(torch.cat([a, b])))
+
+
+def test_native_gate_without_the_extension(monkeypatch):
+    from bigslice_amd import kernels
+    monkeypatch.setattr(kernels, "_C", None)
+    monkeypatch.setattr(kernels, "ALLOW_FALLBACK", False)
+    assert kernels.native(False, "a feature") is False
+    with pytest.raises(RuntimeError, match="not available for a feature"):
+        kernels.native(True, "a feature")
+    monkeypatch.setattr(kernels, "ALLOW_FALLBACK", True)
+    assert kernels.native(True, "a feature") is False
+    assert kernels.native(False, "a feature") is False
+    # a site that asks the gate: a CPU tensor takes the torch path
+    k = torch.tensor([3, 1, 2])
+    assert kernels.radix_sort_keys(k).tolist() == [1, 2, 3]
+    assert sk.unique_sorted(torch.tensor([1, 1, 2])).tolist() == [1, 2]
