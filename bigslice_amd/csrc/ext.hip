@@ -346,9 +346,7 @@ torch::Tensor slot_pids(torch::Tensor keys, int64_t cap,
   return pids;
 }
 
-// Two-level LDS insert (single int64 SUM value): see groupby.hip.  The
-// kernel's sample-adaptive and global-only settings have no caller
-// left: it always runs with its LDS tier on and no hit counter.
+// Two-level LDS insert (single int64 SUM value): see groupby.hip.
 void groupby_insert_lds(torch::Tensor keys, torch::Tensor vals,
                         torch::Tensor tkeys, torch::Tensor tab,
                         torch::Tensor flags, int64_t max_probes,
@@ -365,15 +363,13 @@ void groupby_insert_lds(torch::Tensor keys, torch::Tensor vals,
   if (target_blocks <= 0) target_blocks = 32768;
   int64_t nblocks = std::min<int64_t>((n + THREADS - 1) / THREADS,
                                       target_blocks);
-  int64_t rpb = 0;  // unused by the grid-stride kernel
   hipLaunchKernelGGL(k_groupby_insert_sum_i64_lds, dim3((uint32_t)nblocks),
                      dim3(THREADS), 0, current_stream(),
                      keys.data_ptr<int64_t>(), vals.data_ptr<int64_t>(), n,
                      tkeys.data_ptr<int64_t>(),
                      (long long*)tab.data_ptr<int64_t>(), cap, GB_HASH_SEED,
                      flags.data_ptr<int32_t>(),
-                     flags.data_ptr<int32_t>() + 1, max_probes, rpb,
-                     /*force=*/(int32_t)1, /*global_hits=*/(uint32_t*)nullptr);
+                     flags.data_ptr<int32_t>() + 1, max_probes);
   HIP_CHECK(hipGetLastError());
 }
 

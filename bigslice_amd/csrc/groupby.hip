@@ -10,79 +10,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "columns.h"
+#include "hashtable.h"
 
 #define THREADS 256
-
-// Sentinel marking an empty slot; rows whose key equals the sentinel are
-// accumulated in the reserved extra slot (index == capacity).
-#define GB_SENTINEL 0x8000000000000000LL
-
-enum AggCode : int32_t { AGG_SUM = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_PROD = 3 };
-
-struct ValCols {
-  ColDesc src[MAX_COLS];
-  MutColDesc tab[MAX_COLS];
-  int32_t agg[MAX_COLS];
-  int n;
-};
-
-template <typename T, typename U>
-__device__ __forceinline__ void cas_loop(T* addr, T v, int agg) {
-  U* a = (U*)addr;
-  U old = *a, assumed;
-  do {
-    assumed = old;
-    T cur = __builtin_bit_cast(T, assumed);
-    T nv;
-    switch (agg) {
-      case AGG_MIN: nv = v < cur ? v : cur; break;
-      case AGG_MAX: nv = v > cur ? v : cur; break;
-      default: nv = cur * v; break;
-    }
-    if (nv == cur) return;
-    old = atomicCAS(a, assumed, __builtin_bit_cast(U, nv));
-  } while (old != assumed);
-}
-
-__device__ __forceinline__ void accum(const MutColDesc& t, int64_t slot,
-                                      const ColDesc& s, int64_t i,
-                                      int agg) {
-  switch (t.code) {
-    case DT_I32: {
-      int32_t v = ((const int32_t*)s.ptr)[i];
-      int32_t* a = (int32_t*)t.ptr + slot;
-      if (agg == AGG_SUM) atomicAdd((int*)a, (int)v);
-      else if (agg == AGG_MIN) atomicMin((int*)a, (int)v);
-      else if (agg == AGG_MAX) atomicMax((int*)a, (int)v);
-      else cas_loop<int32_t, unsigned int>(a, v, agg);
-      break;
-    }
-    case DT_I64: {
-      int64_t v = ((const int64_t*)s.ptr)[i];
-      int64_t* a = (int64_t*)t.ptr + slot;
-      if (agg == AGG_SUM)
-        atomicAdd((unsigned long long*)a, (unsigned long long)v);
-      else
-        cas_loop<int64_t, unsigned long long>(a, v, agg);
-      break;
-    }
-    case DT_F32: {
-      float v = ((const float*)s.ptr)[i];
-      float* a = (float*)t.ptr + slot;
-      if (agg == AGG_SUM) atomicAdd(a, v);
-      else cas_loop<float, unsigned int>(a, v, agg);
-      break;
-    }
-    case DT_F64: {
-      double v = ((const double*)s.ptr)[i];
-      double* a = (double*)t.ptr + slot;
-      if (agg == AGG_SUM) atomicAdd(a, v);
-      else cas_loop<double, unsigned long long>(a, v, agg);
-      break;
-    }
-  }
-}
 
 // Compaction: scan the table, appending used slots to the output arrays.
 // Wave-aggregated cursor: one global atomicAdd per wave (64 lanes), not per
@@ -166,21 +96,9 @@ __device__ __forceinline__ void gb_global_insert_sum(
     slot = cap;
   } else {
     uint64_t h = mm3_u64((uint64_t)k, seed) & mask;
-    int64_t probes = 0;
-    for (;;) {
-      long long cur = ((volatile long long*)tkeys)[h];
-      if (cur == k) break;
-      if (cur == GB_SENTINEL) {
-        long long prev = atomicCAS((unsigned long long*)&tkeys[h],
-                                   (unsigned long long)GB_SENTINEL,
-                                   (unsigned long long)k);
-        if (prev == GB_SENTINEL || prev == k) break;
-      }
-      h = (h + 1) & mask;
-      if (++probes >= max_probes) {
-        atomicOr(overflow, 1);
-        return;
-      }
+    if (gb_probe_claim(tkeys, h, mask, k, max_probes) == GB_FULL) {
+      atomicOr(overflow, 1);
+      return;
     }
     slot = (int64_t)h;
   }
@@ -188,25 +106,21 @@ __device__ __forceinline__ void gb_global_insert_sum(
 }
 
 // One row through the LDS table; returns false on LDS-table miss
-// (caller falls back to the global table).  hits counts rows absorbed
-// by an EXISTING LDS entry (the duplicate-rate signal).
-__device__ __forceinline__ bool gb_lds_try(
-    int64_t k, long long v, long long* lk, long long* lv, uint32_t seed,
-    uint32_t* hits) {
+// (caller falls back to the global table).
+__device__ __forceinline__ bool gb_lds_try(int64_t k, long long v,
+                                           long long* lk, long long* lv,
+                                           uint32_t seed) {
   uint32_t h = mm3_u64((uint64_t)k, seed) & (GB_LDS_SLOTS - 1);
   for (int p = 0; p < 4; ++p) {  // short LDS probe chain
     long long cur = lk[h];
-    bool existed = true;
     if (cur == GB_SENTINEL) {
       long long prev = atomicCAS((unsigned long long*)&lk[h],
                                  (unsigned long long)GB_SENTINEL,
                                  (unsigned long long)k);
-      existed = (prev != GB_SENTINEL);
-      cur = existed ? prev : k;
+      cur = (prev == GB_SENTINEL) ? k : prev;
     }
     if (cur == k) {
       atomicAdd((unsigned long long*)&lv[h], (unsigned long long)v);
-      if (existed && hits) atomicAdd(hits, 1u);
       return true;
     }
     h = (h + 1) & (GB_LDS_SLOTS - 1);
@@ -220,52 +134,21 @@ __device__ __forceinline__ bool gb_lds_try(
 extern "C" __global__ void k_groupby_insert_sum_i64_lds(
     const int64_t* keys, const int64_t* vals, int64_t n, int64_t* tkeys,
     long long* tab, int64_t cap, uint32_t seed, int32_t* sentinel_seen,
-    int32_t* overflow, int64_t max_probes, int64_t rows_per_block,
-    int32_t force, uint32_t* global_hits) {
+    int32_t* overflow, int64_t max_probes) {
   __shared__ long long lk[GB_LDS_SLOTS];
   __shared__ long long lv[GB_LDS_SLOTS];
-  __shared__ uint32_t lds_hits;
   for (int i = threadIdx.x; i < GB_LDS_SLOTS; i += blockDim.x) {
     lk[i] = GB_SENTINEL;
     lv[i] = 0;
   }
-  if (threadIdx.x == 0) lds_hits = 0;
   __syncthreads();
   uint64_t gmask = (uint64_t)cap - 1;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t base = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-
-  // Phase 1 (sample): the first SAMPLE_ITERS grid-stride iterations go
-  // through the LDS table, counting rows absorbed by existing entries.
-  // force: -1 = sample-adaptive, 0 = global-only, 1 = always-LDS.
-  const int64_t SAMPLE_ITERS = 16;
-  int64_t sampled = 0;
-  int64_t it = 0;
-  int64_t i = base;
-  if (force == -1) {
-    for (; i < n && it < SAMPLE_ITERS; i += stride, ++it) {
-      int64_t k = keys[i];
-      long long v = (long long)vals[i];
-      ++sampled;
-      if (k == GB_SENTINEL ||
-          !gb_lds_try(k, v, lk, lv, seed, &lds_hits))
-        gb_global_insert_sum(k, v, tkeys, tab, gmask, cap, seed,
-                             sentinel_seen, overflow, max_probes);
-    }
-    __syncthreads();
-  }
-  // Duplicate-rate decision: keep the LDS tier only when >=1/8 of the
-  // block's sampled rows hit an existing entry — otherwise the key
-  // space is too wide for the LDS table and probing it costs latency.
-  (void)sampled;
-  bool use_lds = (force == -1)
-      ? (lds_hits * 8u >= (uint32_t)(SAMPLE_ITERS * blockDim.x))
-      : (force == 1);
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n; i += stride) {
     int64_t k = keys[i];
     long long v = (long long)vals[i];
-    if (k == GB_SENTINEL ||
-        !(use_lds && gb_lds_try(k, v, lk, lv, seed, nullptr)))
+    if (k == GB_SENTINEL || !gb_lds_try(k, v, lk, lv, seed))
       gb_global_insert_sum(k, v, tkeys, tab, gmask, cap, seed,
                            sentinel_seen, overflow, max_probes);
   }
@@ -276,9 +159,6 @@ extern "C" __global__ void k_groupby_insert_sum_i64_lds(
       gb_global_insert_sum(lk[i2], lv[i2], tkeys, tab, gmask, cap, seed,
                            sentinel_seen, overflow, max_probes);
   }
-  // absorption feedback for the host-side mode decision
-  if (global_hits && threadIdx.x == 0 && lds_hits)
-    atomicAdd(global_hits, lds_hits);
 }
 
 // Partition ids from table-slot high bits: the bucket id of the
@@ -314,26 +194,9 @@ extern "C" __global__ void k_groupby_insert(
       slot = cap;
     } else {
       uint64_t h = mm3_u64((uint64_t)k, seed) & mask;
-      int64_t probes = 0;
-      for (;;) {
-        // Plain read first: once the table is warm most probes land on
-        // an already-claimed matching key, and a load is far cheaper
-        // than an atomicCAS.
-        long long cur = ((volatile long long*)tkeys)[h];
-        if (cur == k) break;
-        if (cur == GB_SENTINEL) {
-          long long prev = atomicCAS((unsigned long long*)&tkeys[h],
-                                     (unsigned long long)GB_SENTINEL,
-                                     (unsigned long long)k);
-          if (prev == GB_SENTINEL || prev == k) break;
-        }
-        h = (h + 1) & mask;
-        // A long probe chain means the table is too loaded: signal the
-        // host to grow x2 and re-insert (reference combiner grow policy).
-        if (++probes >= max_probes) {
-          atomicOr(overflow, 1);
-          return;
-        }
+      if (gb_probe_claim(tkeys, h, mask, k, max_probes) == GB_FULL) {
+        atomicOr(overflow, 1);
+        return;
       }
       slot = (int64_t)h;
     }

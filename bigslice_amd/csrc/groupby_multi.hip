@@ -27,7 +27,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "columns.h"
+#include "hashtable.h"
 
 struct MkCols {
   const int64_t* src[MAX_KEY_COLS];  // the batch's key columns
@@ -36,17 +36,6 @@ struct MkCols {
 };
 
 #define GBM_NO_SLOT 0xFFFFFFFFu
-#define GBM_GOLDEN 0x9e3779b97f4a7c15ULL
-
-// murmur3's 64-bit finalizer: a bijection of the 64-bit words.
-__device__ __host__ __forceinline__ uint64_t gbm_fmix64(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdULL;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ULL;
-  h ^= h >> 33;
-  return h;
-}
 
 // One chaining step: the running hash is remixed with every column, so
 // the fingerprint depends on the order of the columns.
@@ -57,12 +46,7 @@ __device__ __host__ __forceinline__ uint64_t gbm_step(uint64_t h,
 
 __device__ __host__ __forceinline__ int64_t gbm_tag(uint64_t h,
                                                      uint64_t fp_mask) {
-  int64_t tag = (int64_t)(h & fp_mask);
-  return tag == GB_SENTINEL ? 0 : tag;
-}
-
-__device__ __host__ __forceinline__ uint64_t gbm_home(int64_t tag) {
-  return gbm_fmix64((uint64_t)tag + GBM_GOLDEN);
+  return gb_tag((int64_t)(h & fp_mask));
 }
 
 template <int NK>
@@ -111,31 +95,16 @@ __global__ void k_gbm_claim(MkCols kc, int64_t n, int64_t* tags,
     int64_t k[MAX_KEY_COLS];
     int64_t tag = gbm_load_tuple<NK>(kc, i, seed, fp_mask, k);
     uint64_t h = gbm_home(tag) & mask;
-    int64_t probes = 0;
-    for (;;) {
-      // Plain read first, as in k_groupby_insert.
-      long long cur = ((volatile long long*)tags)[h];
-      if (cur == tag) break;
-      if (cur == GB_SENTINEL) {
-        long long prev = atomicCAS((unsigned long long*)&tags[h],
-                                   (unsigned long long)GB_SENTINEL,
-                                   (unsigned long long)tag);
-        if (prev == GB_SENTINEL) {
-          // The slot is this thread's: publish the tuple.  Nobody reads
-          // it before the launch ends.
+    const int r = gb_probe_claim(tags, h, mask, tag, max_probes);
+    if (r == GB_CLAIMED) {
+      // The slot is this thread's: publish the tuple.  Nobody reads it
+      // before the launch ends.
 #pragma unroll
-          for (int c = 0; c < N; ++c)
-            if (NK || c < kc.n) kc.tab[c][h] = k[c];
-          break;
-        }
-        if (prev == tag) break;
-      }
-      h = (h + 1) & mask;
-      if (++probes >= max_probes) {
-        atomicOr(overflow, 1);
-        full = true;
-        break;
-      }
+      for (int c = 0; c < N; ++c)
+        if (NK || c < kc.n) kc.tab[c][h] = k[c];
+    } else if (r == GB_FULL) {
+      atomicOr(overflow, 1);
+      full = true;
     }
     slots[i] = full ? GBM_NO_SLOT : (uint32_t)h;
   }

@@ -15,7 +15,7 @@
 //                 ends).  The host then gathers the rows in newrows.
 //   k_idd_lookup  position of every id, -1 when absent.  Read-only.
 //   k_idd_rehash  moves a table into a larger one, one old slot per
-//                 thread; ids are unique, so no equality branch.
+//                 thread; ids are unique, so every probe ends in a claim.
 //
 // No thread waits for another: there is no spin loop.  A row whose probe
 // chain reaches max_probes is left out and raises the overflow counter;
@@ -24,16 +24,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
+#include "hashtable.h"
 
 // counters of k_idd_claim, uint64[3]
 #define IDD_NEW_ROWS 0
 #define IDD_NEW_BYTES 1
 #define IDD_OVERFLOW 2
-
-__device__ __forceinline__ int64_t idd_tag(int64_t id) {
-  return id == GB_SENTINEL ? 0 : id;
-}
 
 __global__ void k_idd_claim(const int64_t* __restrict__ ids, int64_t n,
                             const int64_t* __restrict__ lens, int64_t* tags,
@@ -52,29 +48,13 @@ __global__ void k_idd_claim(const int64_t* __restrict__ ids, int64_t n,
     bool claimed = false;
     uint64_t h = 0;
     if (i < n && !full) {
-      const int64_t tag = idd_tag(ids[i]);
+      const int64_t tag = gb_tag(ids[i]);
       h = gbm_home(tag) & mask;
-      int64_t probes = 0;
-      for (;;) {
-        // Plain read first, as in k_gbm_claim.
-        const long long cur = ((volatile long long*)tags)[h];
-        if (cur == tag) break;
-        if (cur == GB_SENTINEL) {
-          const long long prev = atomicCAS((unsigned long long*)&tags[h],
-                                           (unsigned long long)GB_SENTINEL,
-                                           (unsigned long long)tag);
-          if (prev == GB_SENTINEL) {
-            claimed = true;
-            break;
-          }
-          if (prev == tag) break;
-        }
-        h = (h + 1) & mask;
-        if (++probes >= max_probes) {
-          atomicOr(&counters[IDD_OVERFLOW], 1ull);
-          full = true;
-          break;
-        }
+      const int r = gb_probe_claim(tags, h, mask, tag, max_probes);
+      claimed = (r == GB_CLAIMED);
+      if (r == GB_FULL) {
+        atomicOr(&counters[IDD_OVERFLOW], 1ull);
+        full = true;
       }
     }
     // Wave-aggregated append: one returning atomic per wave and trip.
@@ -110,7 +90,7 @@ __global__ void k_idd_lookup(const int64_t* __restrict__ ids, int64_t n,
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const uint64_t mask = (uint64_t)cap - 1;
   for (; i < n; i += stride) {
-    const int64_t tag = idd_tag(ids[i]);
+    const int64_t tag = gb_tag(ids[i]);
     uint64_t h = gbm_home(tag) & mask;
     int64_t pos = -1;
     // the claim places nothing beyond max_probes slots from home
@@ -139,23 +119,9 @@ __global__ void k_idd_rehash(const int64_t* __restrict__ old_tags,
     const int64_t tag = old_tags[s];
     if (tag == GB_SENTINEL) continue;
     uint64_t h = gbm_home(tag) & mask;
-    int64_t probes = 0;
-    for (;;) {
-      const long long cur = ((volatile long long*)new_tags)[h];
-      if (cur == GB_SENTINEL) {
-        const long long prev = atomicCAS((unsigned long long*)&new_tags[h],
-                                         (unsigned long long)GB_SENTINEL,
-                                         (unsigned long long)tag);
-        if (prev == GB_SENTINEL) {
-          new_ref[h] = old_ref[s];
-          break;
-        }
-      }
-      h = (h + 1) & mask;
-      if (++probes >= max_probes) {
-        atomicOr(overflow, 1);
-        break;
-      }
-    }
+    // ids of a table are unique, so GB_FOUND cannot happen
+    const int r = gb_probe_claim(new_tags, h, mask, tag, max_probes);
+    if (r == GB_CLAIMED) new_ref[h] = old_ref[s];
+    else if (r == GB_FULL) atomicOr(overflow, 1);
   }
 }

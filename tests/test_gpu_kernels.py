@@ -274,6 +274,85 @@ def test_forced_lds_and_global_modes(kernels, monkeypatch):
         assert uk.shape[0] <= 200
 
 
+def _sum_by_key(keys, vals):
+    uk, inv = torch.unique(keys, return_inverse=True)
+    return uk, torch.zeros_like(uk).index_add_(0, inv, vals)
+
+
+@pytest.fixture(scope="module")
+def lds_batch():
+    """20,001 rows (no multiple of 256) over 5000 distinct keys, more
+    than the 1024 LDS slots of the LDS-tier insert, so its 4-probe chain
+    must miss; values in [-10, 10]; then the same batch with 37 rows of
+    the sentinel key.  Each with its torch.unique + index_add_ sums."""
+    g = torch.Generator().manual_seed(19)
+    n, nkeys = 20_001, 5000
+    keys = (torch.arange(n, dtype=torch.int64) % nkeys)[
+        torch.randperm(n, generator=g)] * 0x9E3779B97F4A7 - (1 << 40)
+    vals = torch.randint(-10, 11, (n,), dtype=torch.int64, generator=g)
+    at = torch.randperm(n, generator=g)[:37]
+    skeys = keys.clone()
+    skeys[at] = -2**63
+    keys, vals, skeys = (x.to("cuda:0") for x in (keys, vals, skeys))
+    assert torch.unique(keys).shape[0] == nkeys
+    return {"plain": (keys, vals, _sum_by_key(keys, vals)),
+            "sentinel": (skeys, vals, _sum_by_key(skeys, vals))}
+
+
+def _lds_table_sums(kernels, monkeypatch, keys, vals, cap_hint=None,
+                    blocks=None):
+    """The batch through a GroupTable forced to the LDS-tier insert:
+    (table, keys ascending, their sums)."""
+    monkeypatch.setenv("BIGSLICE_GB_MODE", "lds")
+    if blocks is not None:
+        monkeypatch.setenv("BIGSLICE_GB_LDS_BLOCKS", str(blocks))
+    t = kernels.GroupTable([torch.int64], ["sum"], "cuda:0",
+                           cap_hint=cap_hint)
+    t.insert(keys, [vals])
+    uk, outs = t.finish()
+    assert t._mode == "lds"
+    order = torch.argsort(uk)
+    return t, uk[order], outs[0][order]
+
+
+# blocks=1: one workgroup makes all 79 grid-stride trips
+@pytest.mark.parametrize("blocks", [None, 1])
+def test_lds_insert_miss_path(kernels, monkeypatch, lds_batch, blocks):
+    keys, vals, (want_k, want_v) = lds_batch["plain"]
+    _, uk, sums = _lds_table_sums(kernels, monkeypatch, keys, vals,
+                                  blocks=blocks)
+    assert torch.equal(uk, want_k)
+    assert torch.equal(sums, want_v)
+
+
+def test_lds_insert_sentinel_key(kernels, monkeypatch, lds_batch):
+    keys, vals, (want_k, want_v) = lds_batch["sentinel"]
+    _, uk, sums = _lds_table_sums(kernels, monkeypatch, keys, vals)
+    assert int((uk == -2**63).sum()) == 1
+    assert torch.equal(uk, want_k)
+    assert torch.equal(sums, want_v)
+
+
+def test_lds_insert_overflow_regrows(kernels, monkeypatch, lds_batch):
+    # 5000 keys into 1024 slots: misses and the flush both overflow
+    keys, vals, (want_k, want_v) = lds_batch["plain"]
+    t, uk, sums = _lds_table_sums(kernels, monkeypatch, keys, vals,
+                                  cap_hint=1024)
+    assert t.cap > 1024
+    assert torch.equal(uk, want_k)
+    assert torch.equal(sums, want_v)
+
+
+@pytest.mark.parametrize("n", [1, 255])
+def test_lds_insert_smallest_grids(kernels, monkeypatch, n):
+    keys = torch.full((n,), 7, dtype=torch.int64, device="cuda:0")
+    vals = torch.arange(-3, n - 3, dtype=torch.int64, device="cuda:0")
+    _, uk, sums = _lds_table_sums(kernels, monkeypatch, keys, vals)
+    want_k, want_v = _sum_by_key(keys, vals)
+    assert torch.equal(uk, want_k)
+    assert torch.equal(sums, want_v)
+
+
 def test_radix_sort_reduced_bits(kernels):
     # >1M rows with small non-negative keys triggers the reduced
     # end_bit path; negative keys must fall back to full width.
