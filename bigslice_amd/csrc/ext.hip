@@ -19,6 +19,7 @@
 #include "hash_partition.hip"
 #include "groupby.hip"
 #include "groupby_part.hip"
+#include "groupby_finish.hip"
 #include "sort.hip"
 #include "radix.hip"
 #include "runs.hip"
@@ -596,6 +597,100 @@ std::vector<torch::Tensor> groupby_compact(torch::Tensor tkeys,
                      (unsigned long long*)cursor.data_ptr());
   HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// Workgroups of the fused finish (groupby_finish.hip) and the slots each
+// owns.  The histogram matrix has blocks x nparts counters, written once
+// and read twice, so wide fans take fewer blocks (at most 2^18 counters,
+// 1 MiB); a block owns at least 2048 slots and an even number of them.
+std::pair<int64_t, int64_t> gbf_blocks(int64_t cap, int64_t nparts) {
+  int64_t blocks = std::min<int64_t>(
+      GBF_THREADS, std::max<int64_t>(64, (int64_t(1) << 18) / nparts));
+  blocks = std::min(blocks, (cap + 1 + 2047) / 2048);
+  int64_t spb = (cap + 1 + blocks - 1) / blocks;
+  spb += spb & 1;
+  return {(cap + 1 + spb - 1) / spb, spb};
+}
+
+// Compact the used slots of a table straight into nparts hash partitions
+// (hash_row over the key, seed 0, % nparts).  Returns ([out_keys,
+// out_vals...], host): every output has cap + 1 rows of which the first
+// sum(counts) are set, partition after partition; host is one int64 host
+// tensor {counts[nparts], sentinel_seen, overflow} — the one readback.
+std::tuple<std::vector<torch::Tensor>, torch::Tensor>
+groupby_compact_partition(torch::Tensor tkeys,
+                          std::vector<torch::Tensor> tabs,
+                          torch::Tensor flags, int64_t nparts) {
+  TORCH_CHECK(nparts >= 1 && nparts <= MAX_LDS_PARTS &&
+                  nparts <= GBF_MAX_PARTS,
+              "nparts must be in [1, ", MAX_LDS_PARTS, "]");
+  const int64_t cap = table_cap(tkeys, tabs, flags);
+  TORCH_CHECK(cap <= (int64_t(1) << 31), "capacity above 2^31");
+  FinishCols fc;
+  fc.n = (int)tabs.size();
+  TORCH_CHECK(fc.n <= MAX_COLS, "at most ", MAX_COLS, " value columns");
+  std::vector<torch::Tensor> out;
+  out.push_back(torch::empty({cap + 1}, tkeys.options()));
+  for (int c = 0; c < fc.n; ++c) {
+    const auto st = tabs[c].scalar_type();
+    TORCH_CHECK(st == torch::kInt64 || st == torch::kInt32 ||
+                    st == torch::kFloat32 || st == torch::kFloat64,
+                "unsupported value dtype ", st);
+    out.push_back(torch::empty({cap + 1}, tabs[c].options()));
+    fc.tab[c] = {tabs[c].data_ptr(), dtype_code(tabs[c])};
+    fc.out[c] = {out[c + 1].data_ptr(), dtype_code(tabs[c])};
+  }
+  const auto [blocks, spb] = gbf_blocks(cap, nparts);
+  auto opts32 = tkeys.options().dtype(torch::kInt32);
+  auto hist = torch::empty({nparts * blocks}, opts32);
+  auto totals = torch::empty({nparts}, opts32);
+  auto dev = torch::empty({nparts + 2}, tkeys.options());
+  auto stream = current_stream();
+  const uint32_t np = (uint32_t)nparts;
+  const int32_t* fl = flags.data_ptr<int32_t>();
+  hipLaunchKernelGGL(k_gbf_count, dim3((uint32_t)blocks), dim3(GBF_THREADS),
+                     0, stream, tkeys.data_ptr<int64_t>(), cap, spb, np, fl,
+                     (uint32_t*)hist.data_ptr<int32_t>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gbf_offsets, dim3(np), dim3(GBF_THREADS), 0, stream,
+                     (uint32_t*)hist.data_ptr<int32_t>(), (uint32_t)blocks,
+                     np, fl, (uint32_t*)totals.data_ptr<int32_t>(),
+                     dev.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gbf_write, dim3((uint32_t)blocks), dim3(GBF_THREADS),
+                     0, stream, tkeys.data_ptr<int64_t>(), cap, spb, np, fl,
+                     (const uint32_t*)hist.data_ptr<int32_t>(),
+                     (const uint32_t*)totals.data_ptr<int32_t>(), fc,
+                     out[0].data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  return {out, dev.cpu()};
+}
+
+// Exact count of distinct keys in keys[:rows], minus one, as a device
+// int64 scalar (groupby.hip, "Cardinality sample"): an init and a count
+// launch, no host sync.
+torch::Tensor groupby_sample_distinct(torch::Tensor keys, int64_t rows) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 &&
+              keys.dim() == 1 && keys.stride(0) == 1);
+  TORCH_CHECK(rows >= 1 && rows <= keys.size(0) &&
+                  rows <= (int64_t(1) << 30),
+              "1 <= rows <= min(len(keys), 2^30)");
+  int64_t m = 2;
+  while (m < 2 * rows) m <<= 1;
+  auto tags = torch::empty({m}, keys.options());
+  auto state = torch::empty({2}, keys.options());
+  auto result = state.select(0, 0);
+  auto stream = current_stream();
+  hipLaunchKernelGGL(k_gbs_init, dim3(grid_blocks(m / 2)), dim3(THREADS), 0,
+                     stream, tags.data_ptr<int64_t>(), m,
+                     state.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gbs_count, dim3(grid_blocks((rows + 1) / 2)),
+                     dim3(THREADS), 0, stream, keys.data_ptr<int64_t>(),
+                     rows, tags.data_ptr<int64_t>(), m,
+                     state.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  return result;
 }
 
 // ------------------------------------------- multi-column group-by (K21)
@@ -1628,6 +1723,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("GBP_MAX_BUCKETS") = (int64_t)GBP_MAX_BUCKETS;
   m.def("groupby_compact", &groupby_compact,
         "hash-aggregate table compaction (K9)");
+  m.def("groupby_compact_partition", &groupby_compact_partition,
+        "compact a group-by table straight into hash partitions");
+  m.attr("MAX_LDS_PARTS") = (int64_t)MAX_LDS_PARTS;
+  m.def("groupby_sample_distinct", &groupby_sample_distinct,
+        "distinct keys of a prefix, minus one, as a device scalar");
   m.def("groupby_mk_insert", &groupby_mk_insert,
         "multi-column-key hash-aggregate insert: claim + accumulate (K21)",
         py::arg("keys"), py::arg("vals"), py::arg("aggs"), py::arg("tags"),

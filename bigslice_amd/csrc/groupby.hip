@@ -204,3 +204,76 @@ extern "C" __global__ void k_groupby_insert(
       accum(vals.tab[c], slot, vals.src[c], i, vals.agg[c]);
   }
 }
+
+// Cardinality sample: the exact count of distinct keys among the first
+// `rows` keys of a batch, by claiming each key in a scratch tag table of
+// m >= 2 * rows slots (a power of two: the load never exceeds 0.5, so a
+// chain bounded by m never reports GB_FULL).  state[0] ends at
+// distinct - 1, the number GroupTable._read_sample expects; state[1] is
+// the flag that lets the first sentinel-key row count once (such rows
+// never enter the table).
+extern "C" __global__ void k_gbs_init(int64_t* tags, int64_t m,
+                                      int64_t* state) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    state[0] = -1;
+    state[1] = 0;
+  }
+  const longlong2 empty = {GB_SENTINEL, GB_SENTINEL};
+  for (; 2 * i < m; i += stride) *(longlong2*)(tags + 2 * i) = empty;
+}
+
+__device__ __forceinline__ uint32_t gbs_claim(int64_t k, int64_t* tags,
+                                              uint64_t mask, int32_t* flag) {
+  if (k == GB_SENTINEL)
+    return *(volatile int32_t*)flag == 0 && atomicOr(flag, 1) == 0;
+  uint64_t h = gbm_fmix64((uint64_t)k) & mask;
+  return gb_probe_claim(tags, h, mask, k, (int64_t)mask + 1) == GB_CLAIMED;
+}
+
+// WIDE: two adjacent rows per 16-byte load (keys 16-byte aligned), else
+// one row per load, as gbp_load_rows does.
+template <bool WIDE>
+__device__ __forceinline__ uint32_t gbs_count_rows(const int64_t* keys,
+                                                   int64_t rows,
+                                                   int64_t* tags,
+                                                   uint64_t mask,
+                                                   int32_t* flag) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t mine = 0;
+  if constexpr (WIDE) {
+    for (int64_t i = 2 * t; i < rows; i += 2 * stride) {
+      if (i + 1 < rows) {
+        const longlong2 two = *(const longlong2*)(keys + i);
+        mine += gbs_claim(two.x, tags, mask, flag);
+        mine += gbs_claim(two.y, tags, mask, flag);
+      } else {
+        mine += gbs_claim(keys[i], tags, mask, flag);
+      }
+    }
+  } else {
+    for (int64_t i = t; i < rows; i += stride)
+      mine += gbs_claim(keys[i], tags, mask, flag);
+  }
+  return mine;
+}
+
+extern "C" __global__ __launch_bounds__(THREADS) void k_gbs_count(
+    const int64_t* keys, int64_t rows, int64_t* tags, int64_t m,
+    int64_t* state) {
+  __shared__ uint32_t claimed;
+  if (threadIdx.x == 0) claimed = 0;
+  __syncthreads();
+  const uint64_t mask = (uint64_t)m - 1;
+  int32_t* flag = (int32_t*)(state + 1);
+  const uint32_t mine =
+      ((uintptr_t)keys & 15) == 0
+          ? gbs_count_rows<true>(keys, rows, tags, mask, flag)
+          : gbs_count_rows<false>(keys, rows, tags, mask, flag);
+  if (mine) atomicAdd(&claimed, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && claimed)
+    atomicAdd((unsigned long long*)state, (unsigned long long)claimed);
+}

@@ -51,6 +51,10 @@ class Options:
                                 # workgroup, 0 = the extension's rule
     lds_blocks: int = 4096      # BIGSLICE_GB_LDS_BLOCKS: grid cap, "lds"
     sample_rows: int = 1 << 19  # BIGSLICE_GB_SAMPLE_ROWS
+    sample: str = "hash"        # BIGSLICE_GB_SAMPLE: hash | sort (the
+                                # distinct count of the sampled prefix)
+    finish_part: bool = True    # BIGSLICE_GB_FINISH_PART: the table
+                                # finishes straight into partitions
     debug: bool = False         # BIGSLICE_GB_DEBUG: chooser trace
 
     @classmethod
@@ -66,6 +70,9 @@ class Options:
             lds_blocks=int(env.get("BIGSLICE_GB_LDS_BLOCKS", "4096")),
             sample_rows=int(env.get("BIGSLICE_GB_SAMPLE_ROWS",
                                     str(1 << 19))),
+            sample=("sort" if env.get("BIGSLICE_GB_SAMPLE") == "sort"
+                    else "hash"),
+            finish_part=env.get("BIGSLICE_GB_FINISH_PART", "1") == "1",
             debug=bool(env.get("BIGSLICE_GB_DEBUG")))
 
 
@@ -306,6 +313,8 @@ class GroupTable(HashTable):
         self._sample_batch_n = 0
         self._sample_ne = None  # device scalar: key changes in the sample
         self._key_estimate: Optional[float] = None
+        self._settled = False  # _settle has run
+        self._done = None  # its result, when that is not in the table
 
     @property
     def _sum_i64(self) -> bool:
@@ -336,20 +345,27 @@ class GroupTable(HashTable):
                 and all(dt in _GB_VAL_DTYPES for dt in self.val_dtypes))
 
     def _start_sample(self, keys: torch.Tensor) -> None:
-        """Cardinality sample: sorted prefix of the first large batch.
-        Launched WITHOUT a host sync (the device scalar is read at the
-        next insert or at finish, when the count is long done), so the
-        streaming hot path pays only ~0.1 ms of overlapped GPU time."""
+        """Cardinality sample: the exact count of distinct keys in a
+        prefix of the first large batch, minus one, as a device scalar.
+        Launched WITHOUT a host sync (the scalar is read at the next
+        insert or at finish).  "hash" claims the keys in a scratch tag
+        table (csrc/groupby.hip, two launches); "sort" sorts the prefix
+        and counts the key changes (24 launches at 2^19 rows): the same
+        number either way."""
         self._sample_forced = forced_mode(self.opts, self._sum_i64)
         if self._sample_forced:
             return
         prefix = min(keys.shape[0], self.opts.sample_rows)
+        self._sample_n = prefix
+        self._sample_batch_n = keys.shape[0]
+        if self.opts.sample == "hash" and native(keys.is_cuda, "groupby"):
+            self._sample_ne = _k._C.groupby_sample_distinct(
+                keys.contiguous(), prefix)
+            return
         # probe=False: the probe's count readback would sync the
         # stream; the sample must stay fire-and-forget
         sk = _k._C.radix_sort_keys(keys[:prefix].contiguous(),
                                 probe=False)
-        self._sample_n = prefix
-        self._sample_batch_n = keys.shape[0]
         self._sample_ne = (sk[1:] != sk[:-1]).sum()  # device scalar
 
     def _read_sample(self) -> str:
@@ -460,20 +476,64 @@ class GroupTable(HashTable):
         stats.DEFAULT.add("combiner/keys", int(uk.shape[0]))
         return uk, outs
 
-    def finish(self):
-        """Returns (keys, [vals]) of the aggregated groups."""
+    def _settle(self):
+        """What finish does before it reads the table, once: the pending
+        sample, the deferred batches.  Returns (keys, [vals]) when the
+        result is not in a table (sort mode without a provisional table,
+        no rows), else None."""
         from ..utils import stats
+        if self._settled:
+            return self._done
+        self._settled = True
         stats.DEFAULT.add("combiner/records", self.rows)
         if self._mode == "pending":
             self._mode = self._read_sample()
         if self._deferred:
-            done = self._finish_deferred()
-            if done is not None:
-                return done
-        if self.cap is None:
+            self._done = self._finish_deferred()
+        if self._done is None and self.cap is None:
             empty = torch.empty(0, dtype=torch.int64, device=self.device)
-            return empty, [torch.empty(0, dtype=dt, device=self.device)
-                           for dt in self.val_dtypes]
+            self._done = empty, [
+                torch.empty(0, dtype=dt, device=self.device)
+                for dt in self.val_dtypes]
+        return self._done
+
+    def finish_partitioned(self, nparts: int):
+        """finish() for a shuffle producer: the aggregated groups split
+        into nparts hash partitions (hash_row over the key, seed 0,
+        % nparts: what hash_partition gives), as a list of (keys, [vals])
+        slices of one buffer, by one pass over the table and one
+        readback (csrc/groupby_finish.hip).  None where that does not
+        apply (BIGSLICE_GB_FINISH_PART=0, a fan-out the kernels do not
+        take, a result that is not in a table): finish() then gives the
+        result, as ever."""
+        from ..utils import stats
+        if not (self.opts.finish_part
+                and 1 <= nparts <= _k._C.MAX_LDS_PARTS):
+            return None
+        if self._settle() is not None:
+            return None
+        while True:
+            outs, host = _k._C.groupby_compact_partition(
+                self.tkeys, self.tabs, self.flags, nparts)
+            *counts, _, overflow = host.tolist()
+            if overflow:
+                self._regrow()
+                continue
+            self.batches = []
+            stats.DEFAULT.add("combiner/keys", sum(counts))
+            parts, off = [], 0
+            for c in counts:
+                parts.append((outs[0][off:off + c],
+                              [o[off:off + c] for o in outs[1:]]))
+                off += c
+            return parts
+
+    def finish(self):
+        """Returns (keys, [vals]) of the aggregated groups."""
+        from ..utils import stats
+        done = self._settle()
+        if done is not None:
+            return done
         while True:
             outs, (nkeys, sentinel_seen, overflow) = self._compact()
             if overflow:

@@ -385,6 +385,29 @@ class TensorAggregator:
             vals = [torch.cat([sv, v]) for sv, v in zip(self.vals, vals)]
         self.keys, self.vals = _combine_once(keys, vals, self.agg)
 
+    def result_partitions(self, nparts: int, chunk: int):
+        """The result already split by the default partitioner, for a
+        shuffle producer: per partition a list of frames of at most
+        `chunk` rows, all with one combined_id.  Only a GroupTable gives
+        that (GroupTable.finish_partitioned); None for pass-through
+        frames, without a table, for a multi-column key, on a CPU and
+        wherever the table declines: result_frames + split_frame then
+        give the same buckets."""
+        if (self._pt_frames is not None or self._table is None
+                or self.nkey != 1 or not self.device.startswith("cuda")):
+            return None
+        self._pending.flush(self._table_insert)
+        parts = self._table.finish_partitioned(nparts)
+        if parts is None:
+            return None
+        import uuid
+        cid = uuid.uuid4().int & ((1 << 63) - 1)
+        return [[Frame([keys[off:off + chunk]] +
+                       [v[off:off + chunk] for v in vals],
+                       self.schema.prefix, combined_id=cid)
+                 for off in range(0, keys.shape[0], chunk)]
+                for keys, vals in parts]
+
     def result_frames(self, chunk: int):
         if self._pt_frames is not None:
             # single pre-combined stream: identity (keys already unique)

@@ -56,6 +56,24 @@ def split_frame(frame: Frame, num_partitions: int,
     return out
 
 
+def combined_buckets(agg, num_partitions: int,
+                     chunk: int) -> List[List[Frame]]:
+    """Per-partition frame lists of a combine-first aggregator's result
+    under the default partitioner.  An aggregator whose table finishes
+    straight into partitions (TensorAggregator.result_partitions) gives
+    them itself; otherwise its result frames are split one by one."""
+    fused = getattr(agg, "result_partitions", None)
+    buckets = fused(num_partitions, chunk) if fused is not None else None
+    if buckets is not None:
+        return buckets
+    buckets = [[] for _ in range(num_partitions)]
+    for f in agg.result_frames(chunk):
+        for pi, pf in enumerate(split_frame(f, num_partitions, None)):
+            if pf is not None and len(pf):
+                buckets[pi].append(pf)
+    return buckets
+
+
 class SharedPhaseCombiner:
     """Per-GPU shared combiner for one shuffle phase (the reference's
     machine-combiners mode, exec/session.go:166-176 + bigmachine.go
@@ -107,14 +125,8 @@ class SharedPhaseCombiner:
             cur = torch.cuda.current_stream()
             for ev in self.events:
                 cur.wait_event(ev)
-        buckets: List[List[Frame]] = \
-            [[] for _ in range(self.num_partitions)]
-        for f in self.agg.result_frames(self.chunk * 4):
-            for pi, pf in enumerate(split_frame(f, self.num_partitions,
-                                                None)):
-                if pf is not None and len(pf):
-                    buckets[pi].append(pf)
-        return buckets
+        return combined_buckets(self.agg, self.num_partitions,
+                                self.chunk * 4)
 
 
 class PartitionWriter:
@@ -174,12 +186,8 @@ class PartitionWriter:
     def finish(self) -> List[List[Frame]]:
         """Per-partition frame lists."""
         if self.agg is not None:
-            for f in self.agg.result_frames(self.chunk * 4):
-                parts = split_frame(f, self.num_partitions, None)
-                for pi, pf in enumerate(parts):
-                    if pf is not None and len(pf):
-                        self.buckets[pi].append(pf)
-            return self.buckets
+            return combined_buckets(self.agg, self.num_partitions,
+                                    self.chunk * 4)
         if self.aggs is not None:
             return [list(a.result_frames(self.chunk)) for a in self.aggs]
         return self.buckets

@@ -8,6 +8,8 @@
   python -m bigslice_amd.tools.microprof runs_multi --rows 8388608
   python -m bigslice_amd.tools.microprof iddict --rows 8388608
   python -m bigslice_amd.tools.microprof bytes_gather
+  python -m bigslice_amd.tools.microprof sample --nkeys 1000000
+  python -m bigslice_amd.tools.microprof finish --nkeys 1000000 --nparts 8
 
 Times each kernel phase with hipEvents over --iters iterations.  Keep
 runs short: this is the target for `rocprofv3 --pmc ... -- ...`.
@@ -270,9 +272,61 @@ def bytes_gather_ab(dev, g, iters, rows=1 << 20):
     return out
 
 
+def sample_ab(dev, g, iters, rows, nkeys):
+    """The cardinality sample of GroupTable over one prefix of `rows`
+    keys from `nkeys`: the sorted prefix with its key-change count (24
+    launches at 2^19 rows) against the one counting kernel (2 launches).
+    Wall time per call, the readback of the count included, as
+    _read_sample pays it."""
+    C = kernels._C
+    keys = torch.randint(0, nkeys, (rows,), dtype=torch.int64, device=dev,
+                         generator=g)
+
+    def by_sort():
+        sk = C.radix_sort_keys(keys, probe=False)
+        return int((sk[1:] != sk[:-1]).sum().item())
+
+    def by_hash():
+        return int(C.groupby_sample_distinct(keys, rows).item())
+    assert by_sort() == by_hash()
+    return {"which": "sample", "rows": rows, "nkeys": nkeys,
+            "distinct": by_hash() + 1,
+            "sort_ms": timeit(by_sort, iters),
+            "hash_ms": timeit(by_hash, iters)}
+
+
+def finish_ab(dev, g, iters, nkeys, cap, nparts):
+    """Finish of one filled table of `cap` slots and `nkeys` keys into
+    `nparts` partitions: compaction, its readback, hash_partition and its
+    readback (GroupTable.finish + split_frame) against the fused
+    groupby_compact_partition and its one readback."""
+    C = kernels._C
+    cap = cap or kernels._next_pow2(4 * nkeys)
+    t = kernels.GroupTable([torch.int64], ["sum"], dev)
+    t._alloc(cap)
+    keys = torch.randperm(nkeys, dtype=torch.int64, device=dev, generator=g)
+    C.groupby_insert(keys, [torch.ones_like(keys)], t.codes, t.tkeys,
+                     t.tabs, t.flags, kernels.MAX_PROBES)
+    assert t.flags.tolist() == [0, 0]
+
+    def old():
+        outs, (n, _, _) = t._compact()
+        cols = [o[:n] for o in outs]
+        return C.hash_partition(cols, [cols[0]], nparts, 0)[1].tolist()
+
+    def fused():
+        host = C.groupby_compact_partition(t.tkeys, t.tabs, t.flags,
+                                           nparts)[1]
+        return host.tolist()[:nparts]
+    assert old() == fused()
+    return {"which": "finish", "nkeys": nkeys, "cap": cap, "nparts": nparts,
+            "old_ms": timeit(old, iters), "fused_ms": timeit(fused, iters)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", choices=["groupby", "groupby_part", "insert",
+                                      "sample", "finish",
                                       "groupby_multi", "runs_multi",
                                       "partition", "hash", "compact",
                                       "sortcombine", "sortcombine2", "hashbytes",
@@ -300,6 +354,14 @@ def main():
         return
     if args.which == "bytes_gather":
         print(json.dumps(bytes_gather_ab(dev, g, args.iters)))
+        return
+    if args.which == "sample":
+        print(json.dumps(sample_ab(dev, g, args.iters,
+                                   min(args.rows, 1 << 19), args.nkeys)))
+        return
+    if args.which == "finish":
+        print(json.dumps(finish_ab(dev, g, args.iters, args.nkeys, args.cap,
+                                   args.nparts)))
         return
     if args.which == "groupby_multi":
         print(json.dumps(groupby_multi(dev, g, args.iters, args.rows,
