@@ -31,6 +31,7 @@
 #include "groupby_multi.hip"
 #include "iddict.hip"
 #include "bytes_gather.hip"
+#include "bytes_order.hip"
 
 namespace {
 
@@ -1689,6 +1690,71 @@ std::vector<torch::Tensor> bytes_gather(torch::Tensor data,
   return {out_data, out_offsets};
 }
 
+// ------------------------------------------- byte-order refinement (K24)
+
+// Round-w keys of rows `rows` of the BYTES column (data, offsets): the
+// bytes [7w, 7w+7) big-endian over the count of real ones, top bit
+// flipped (bytes_order.hip).  offsets may be a slice; a row index
+// outside the column has length 0.  max_blocks > 0 caps the grid (the
+// tests take the grid-stride loop with it at small sizes).
+torch::Tensor bytes_order_keys(torch::Tensor data, torch::Tensor offsets,
+                               torch::Tensor rows, int64_t w,
+                               int64_t max_blocks) {
+  TORCH_CHECK(data.is_cuda() && data.is_contiguous() && data.dim() == 1 &&
+                  data.scalar_type() == torch::kUInt8,
+              "bytes_order_keys: contiguous uint8 device data required");
+  TORCH_CHECK(offsets.is_cuda() && offsets.is_contiguous() &&
+                  offsets.dim() == 1 && offsets.size(0) >= 1 &&
+                  offsets.scalar_type() == torch::kInt64,
+              "bytes_order_keys: contiguous int64 device offsets required");
+  TORCH_CHECK(rows.is_cuda() && rows.dim() == 1 &&
+                  rows.scalar_type() == torch::kInt64,
+              "bytes_order_keys: int64 device row indices required");
+  TORCH_CHECK(w >= 0 && w < (int64_t(1) << 59), "bytes_order_keys: bad round");
+  rows = rows.contiguous();
+  const int64_t m = rows.size(0);
+  auto keys = torch::empty({m}, rows.options());
+  if (m == 0) return keys;
+  int blocks = grid_blocks(m, BO_BLOCK);
+  if (max_blocks > 0 && max_blocks < blocks) blocks = (int)max_blocks;
+  hipLaunchKernelGGL(k_bo_keys, dim3(blocks),
+                     dim3(BO_BLOCK), 0, current_stream(),
+                     data.data_ptr<uint8_t>(), data.size(0),
+                     offsets.data_ptr<int64_t>(), offsets.size(0) - 1,
+                     rows.data_ptr<int64_t>(), m, w,
+                     keys.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
+  return keys;
+}
+
+// One refinement pass over slots sorted by (grp, key): {head int64[m],
+// stay bool[m]}.  head[j] is j where slot j starts a (grp, key) group,
+// else 0; stay[j] is set where slot j is tied with a neighbour and its
+// key says 7 real bytes.
+std::vector<torch::Tensor> bytes_order_refine(torch::Tensor grp,
+                                              torch::Tensor key) {
+  const int64_t m = int64_cols({grp, key}, 2, 2, "grp and key");
+  auto head = torch::empty({m}, grp.options());
+  auto stay = torch::empty({m}, grp.options().dtype(torch::kBool));
+  if (m == 0) return {head, stay};
+  // a thread moves its slots with 16-byte loads and stores
+  if (((uintptr_t)grp.data_ptr<int64_t>() & 15) != 0) grp = grp.clone();
+  if (((uintptr_t)key.data_ptr<int64_t>() & 15) != 0) key = key.clone();
+  TORCH_CHECK((((uintptr_t)grp.data_ptr<int64_t>() |
+                (uintptr_t)key.data_ptr<int64_t>() |
+                (uintptr_t)head.data_ptr<int64_t>()) & 15) == 0 &&
+                  ((uintptr_t)stay.data_ptr<bool>() & 3) == 0,
+              "bytes_order_refine: 16-byte aligned tensors required");
+  const int64_t ntiles = (m + BO_TILE - 1) / BO_TILE;
+  TORCH_CHECK(ntiles < (int64_t(1) << 31), "bytes_order_refine: too large");
+  hipLaunchKernelGGL(k_bo_refine, dim3((uint32_t)ntiles), dim3(BO_BLOCK), 0,
+                     current_stream(), grp.data_ptr<int64_t>(),
+                     key.data_ptr<int64_t>(), m, head.data_ptr<int64_t>(),
+                     reinterpret_cast<uint8_t*>(stay.data_ptr<bool>()));
+  HIP_CHECK(hipGetLastError());
+  return {head, stay};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1786,4 +1852,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("data"), py::arg("offsets"), py::arg("rows"),
         py::arg("total") = -1);
   m.attr("BYTES_GATHER_TILE_BYTES") = (int64_t)BG_TILE;
+  m.def("bytes_order_keys", &bytes_order_keys,
+        "round keys of the byte-order refinement of a BYTES column (K24)",
+        py::arg("data"), py::arg("offsets"), py::arg("rows"), py::arg("w"),
+        py::arg("max_blocks") = 0);
+  m.def("bytes_order_refine", &bytes_order_refine,
+        "head markers and stays-active flags of sorted refinement slots");
+  m.attr("BYTES_ORDER_BLOCK") = (int64_t)BO_BLOCK;
+  m.attr("BYTES_ORDER_TILE_SLOTS") = (int64_t)BO_TILE;
 }

@@ -213,6 +213,21 @@ class BytesColumn:
             vals.append(v - (1 << 64) if v >= (1 << 63) else v)
         return torch.tensor(vals, dtype=torch.int64)
 
+    def order_ranks(self) -> torch.Tensor:
+        """int64 byte-order ranks per row (K24, kernels/bytesort.py):
+        rank[i] < rank[j] iff row i < row j as bytes, equal for equal
+        rows (rows of equal id: exact up to the id collision above), not
+        dense.  Device kernels on a GPU column, the same result in torch
+        on a host column."""
+        from .kernels import bytesort
+        return bytesort.order_ranks(self)
+
+    def argsort(self) -> torch.Tensor:
+        """The stable permutation into byte order, the order of
+        bytes.__lt__ (ids64 orders by hash instead)."""
+        from .kernels import sortedkeys
+        return sortedkeys.lex_argsort([self.order_ranks()])
+
     def hash32(self, seed: int) -> torch.Tensor:
         """Row murmur3-32 (the K3/K17 partition hash), bit-identical to
         the host OBJECT string path so placement is reproducible."""

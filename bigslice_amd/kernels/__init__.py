@@ -112,6 +112,11 @@ from .groupby_multi import MultiKeyTable, fingerprint64  # noqa: E402,F401
 
 from .iddict import IdDictionary, bytes_gather  # noqa: E402,F401
 
+# -- byte-order ranks of a BYTES column (K24) ------------------------------
+
+from .bytesort import (  # noqa: E402,F401
+    distinct_order_ranks, order_ranks, round_keys)
+
 
 # -- sort (K6) -------------------------------------------------------------
 

@@ -11,6 +11,9 @@ Two paths:
   (sort, boundary detection) runs in HIP/rocPRIM via frame sort kernels.
   Keys of 2 to 8 int64/int32 columns take the same steps over tuples
   (K22): lexicographic sort, tuple run boundaries, tuple searchsorted.
+  Keys with BYTES columns (K24) group by the 64-bit ids of the strings
+  through those same steps, and the distinct keys of the union are then
+  put into byte order by BytesColumn.order_ranks().
 """
 
 from __future__ import annotations
@@ -21,7 +24,7 @@ from typing import List
 import torch
 
 from ..frame import Frame, SegmentedColumn
-from ..schema import OBJECT, Schema, common_key_schema
+from ..schema import BYTES, OBJECT, Schema, common_key_schema
 from ..sliceio import IterReader, Reader
 from .slice_base import Dep, Name, Slice, TaskContext
 
@@ -96,9 +99,18 @@ class Cogroup(Slice):
         OBJECT column in any dep.  A composite key (K22): int64/int32
         key columns (at most MAX_KEY_COLS, checked with the extension's
         constant when the reader is made) and dense torch columns
-        otherwise."""
+        otherwise.  A key with BYTES columns (K24): 1 to MAX_KEY_COLS
+        key columns, at least one of them BYTES and the others
+        int64/int32, and dense torch value columns."""
         nkey = self.schema.prefix
         dep_dts = [d.slice.schema.dtypes for d in self.deps]
+        if any(dt == BYTES for dts in dep_dts for dt in dts[:nkey]):
+            return all(
+                any(dt == BYTES for dt in dts[:nkey])
+                and all(dt == BYTES or dt in (torch.int64, torch.int32)
+                        for dt in dts[:nkey])
+                and all(isinstance(dt, torch.dtype) for dt in dts[nkey:])
+                for dts in dep_dts)
         if nkey == 1:
             return (dep_dts[0][0] == torch.int64
                     and all(dt != OBJECT for dts in dep_dts for dt in dts))
@@ -113,21 +125,36 @@ class Cogroup(Slice):
         not 0 and the extension is there (missing, it is an error unless
         the eager fallback is allowed; then the host path runs).  A
         single key costs its reader nothing here: its eight shards share
-        the interpreter and the path is host-bound on small inputs."""
+        the interpreter and the path is host-bound on small inputs.  A
+        key with BYTES columns, of any width, is under
+        BIGSLICE_COGROUP_BYTES in the same way."""
+        from .. import kernels
+        from ..kernels.groupby_multi import MAX_KEY_COLS
+        if self._device_shape and self._bytes_key_cols():
+            if os.environ.get("BIGSLICE_COGROUP_BYTES", "1") == "0":
+                return False
+            return (self.schema.prefix <= MAX_KEY_COLS
+                    and kernels.native(True, "cogroup over bytes keys"))
         if not self._device_shape or self.schema.prefix == 1:
             return self._device_shape
         if os.environ.get("BIGSLICE_COGROUP_MULTIKEY", "1") == "0":
             return False
-        from .. import kernels
-        from ..kernels.groupby_multi import MAX_KEY_COLS
         return (self.schema.prefix <= MAX_KEY_COLS
                 and kernels.native(True, "cogroup over multi-column keys"))
+
+    def _bytes_key_cols(self) -> List[int]:
+        """The BYTES columns of the key prefix."""
+        return [c for c, dt in enumerate(
+            self.schema.dtypes[:self.schema.prefix]) if dt == BYTES]
 
     def _device_gen(self, dep_readers, ctx):
         """Sort-merge cogroup over a key of nkey integer columns."""
         from ..kernels import sortedkeys as sk
         from ..sortio import sort_frame
 
+        if self._bytes_key_cols():
+            yield from self._device_gen_bytes(dep_readers, ctx)
+            return
         device = ctx.device
         nkey = self.schema.prefix
         # 1. sort each dep side by key once.  One key column: the direct
@@ -176,15 +203,118 @@ class Cogroup(Slice):
         for off in range(0, len(frame), ctx.chunk):
             yield frame.slice(off, min(off + ctx.chunk, len(frame)))
 
+    def _device_gen_bytes(self, dep_readers, ctx):
+        """Sort-merge cogroup over a key with BYTES columns (K24).  Rows
+        group by id tuples — every BYTES key column stands in as its
+        ids64() — through the K22 steps; one exemplar string per
+        distinct tuple is carried along, and the union's tuples, few
+        next to the rows, are put into byte order at the end.  The keys
+        come back in the host path's order: ascending, BYTES columns as
+        bytes.__lt__ orders them.  Grouping is by id: exact up to the
+        2^-64-per-pair collision BytesColumn documents."""
+        from ..frame import BytesColumn
+        from ..kernels import bytesort
+        from ..kernels import sortedkeys as sk
+        from ..utils import stats
+
+        stats.DEFAULT.add("cogroup/bytes_device", 1)
+        device = ctx.device
+        nkey = self.schema.prefix
+        bcols = self._bytes_key_cols()
+        # 1. per dep: sort a permutation by id tuple; move the value
+        # columns by it, never the strings of every row
+        dep_runs, dep_vals, dep_ex = [], [], []
+        for r in dep_readers:
+            frames = [f for f in r if len(f)]
+            if not frames:
+                dep_runs.append(None)
+                dep_vals.append(None)
+                dep_ex.append(None)
+                continue
+            f = Frame.concat(frames)
+            idcols = [c.ids64() if isinstance(c, BytesColumn) else c
+                      for c in f.columns[:nkey]]
+            perm = sk.lex_argsort(idcols)
+            run = sk.runs_multi([c[perm] for c in idcols])
+            dep_runs.append(run)
+            dep_vals.append([v[perm] for v in f.columns[nkey:]])
+            # one exemplar string per run
+            first = perm[run[1]]
+            dep_ex.append([f.columns[c].gather(first) for c in bcols])
+        uniq_tuples = [r[0] for r in dep_runs if r is not None]
+        if not uniq_tuples:
+            return
+        # 2. sorted-unique union of the per-dep distinct id tuples
+        if len(uniq_tuples) == 1:
+            union_cols = uniq_tuples[0]
+        elif len(uniq_tuples) == 2:
+            union_cols = sk.merge_sorted_unique_multi(*uniq_tuples)
+        else:
+            union_cols = sk.unique_sorted_multi(sk.lex_sort_keys(
+                [torch.cat(cs) for cs in zip(*uniq_tuples)]))
+        u = union_cols[0].shape[0]
+        # 3. per-dep segments, and for every union tuple the row of one
+        # exemplar among the deps' exemplars laid end to end; both from
+        # one search of the dep's tuples in the union
+        src = torch.zeros(u, dtype=torch.int64, device=device)
+        seg_cols = []
+        base = 0
+        for di, run in enumerate(dep_runs):
+            if run is None:
+                empty_vals = [
+                    torch.empty(0, dtype=dt, device=device)
+                    for dt in self.deps[di].slice.schema.dtypes[nkey:]]
+                zeros = torch.zeros(u, dtype=torch.int64, device=device)
+                seg_cols.extend(SegmentedColumn(ev, zeros, zeros)
+                                for ev in empty_vals)
+                continue
+            nu = run[0][0].shape[0]
+            own = torch.arange(base, base + nu, dtype=torch.int64,
+                               device=device)
+            idx = (sk.lex_searchsorted(union_cols, run[0])
+                   if nu != u else None)
+            if idx is None:
+                src = own
+            else:
+                src[idx] = own
+            seg_cols.extend(_segments_for(run, dep_vals[di], union_cols,
+                                          sk.lex_searchsorted, idx=idx))
+            base += nu
+        have = [ex for ex in dep_ex if ex is not None]
+        # 4. byte order: ranks of the union's strings, then one
+        # lexicographic sort of (rank or integer column, ...)
+        sort_cols = list(union_cols)
+        exemplars = {}
+        for bi, c in enumerate(bcols):
+            ex = _concat_bytes([e[bi] for e in have]).gather(src)
+            exemplars[c] = ex
+            sort_cols[c] = bytesort.order_ranks(ex, ids=union_cols[c])
+        perm = sk.lex_argsort(sort_cols)
+        # 5. the output frame, selected once
+        out_cols = [exemplars[c].gather(perm) if c in exemplars
+                    else union_cols[c][perm] for c in range(nkey)]
+        out_cols.extend(sc.select(perm) for sc in seg_cols)
+        frame = Frame(out_cols, prefix=nkey)
+        for off in range(0, len(frame), ctx.chunk):
+            yield frame.slice(off, min(off + ctx.chunk, len(frame)))
+
+
+def _concat_bytes(cols):
+    """BytesColumns laid end to end."""
+    if len(cols) == 1:
+        return cols[0]
+    return Frame.concat([Frame([c], 1) for c in cols]).columns[0]
+
 
 def _key_sort(k):
     return k
 
 
-def _segments_for(run, value_cols, union_cols, search):
+def _segments_for(run, value_cols, union_cols, search, idx=None):
     """Per-value-column SegmentedColumns aligned with the union's key
     tuples, built from the dep's precomputed runs; search is
-    sortedkeys.lex_searchsorted.  Keys the dep lacks get (0, 0) = empty
+    sortedkeys.lex_searchsorted, idx its result for the dep's tuples
+    when the caller has it.  Keys the dep lacks get (0, 0) = empty
     segments."""
     uniq_cols, starts, ends = run
     u = union_cols[0].shape[0]
@@ -192,7 +322,8 @@ def _segments_for(run, value_cols, union_cols, search):
         # uniq is a subset of union of equal sortedness; sizes equal
         # implies identical key sets, so scatter only when they differ
         dev = union_cols[0].device
-        idx = search(union_cols, uniq_cols)
+        if idx is None:
+            idx = search(union_cols, uniq_cols)
         s = torch.zeros(u, dtype=torch.int64, device=dev)
         e = torch.zeros(u, dtype=torch.int64, device=dev)
         s[idx] = starts
